@@ -2,6 +2,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
                     [--config cfg3|cfg1|cfg2|cfg4|cfg5|xz|7z] [--streams S]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one launch of the batch decode kernel over the whole per-GPU
 batch (inputs already resident in HBM, outputs written to HBM).  Default
@@ -16,10 +17,24 @@ every rank its own 65,536-stream batch, --scaling strong splits one fixed
 65,536-stream batch over the ranks.  Timing is barrier + synchronize
 bracketed, MAX over ranks; value = all ranks' decompressed bytes / that time.
 
+A plain run does what the headline needs and no more: it builds (or loads the
+cached) workload, warms up, times the K steps, verifies every timed launch
+against the plaintext, writes the outputs where --dump-outputs DIR asks for
+them, and prints the result line.  Every other leg below runs only with --full.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed
+step left for its caller as DIR/<name>.npy: `results` (float64, one row of
+res / status / destLen / srcLen per stream), `decoded` (float32, the decoded
+bytes; an output above 8 MiB as a fixed seeded sample of 2,048 whole 4 KiB
+pieces, one row each) and, per config, the checksums of the whole output.  The
+workload is generated from fixed seeds, so two builds given the same arguments
+decode the same inputs and their dumps compare array for array.
+
 Rank 0 prints ONE JSON line.  It carries the live roofline of the decode
-kernel (HIP events on the launch stream), the issue-side counters of the
-committed rocprof profile, an end-to-end (H2D + decode + D2H, pinned host
-buffers) rate, and the CPU baseline: the reference's own LzmaDecode
+kernel (HIP events on the launch stream) and the issue-side counters of the
+committed rocprof profile; with --full also an end-to-end (H2D + decode + D2H,
+pinned host buffers) rate, the CRC-32 leg, short runs of configs 1, 2, 4 and 5
+under `secondary`, and the CPU baseline: the reference's own LzmaDecode
 (oracle/_ref/libref_lzma.so, LzmaDec.c compiled in place, "kind": "reference";
 the oracle restatement oracle/liboracle.so, "kind": "port", where that library
 is absent) timed on every host core this job may use over the same batch, on
@@ -288,6 +303,34 @@ def step_results(d_res_steps):
     return np.stack([np.frombuffer(raw[k].tobytes(), dtype=RES_DT) for k in range(raw.shape[0])])
 
 
+DUMP_PIECE = 4096    # --dump-outputs: bytes per sampled piece of a large output
+DUMP_PIECES = 2048   # pieces sampled (8 MiB of output, 32 MiB as float32)
+
+
+def dump_outputs(path, torch, d_out, nbytes, results, extra=None):
+    """--dump-outputs: the last timed step's outputs as path/<name>.npy.
+    `results` (one RES_DT row per stream) -> float64 (streams, 4); the first
+    nbytes of the device output d_out -> `decoded`, float32: all of it up to
+    DUMP_PIECES x DUMP_PIECE bytes, else that many whole pieces drawn once from
+    a fixed seed (the same pieces in every run), one row per piece in offset
+    order; `extra`: further named arrays (checksums of the whole output), as
+    float64.  Every value is an integer both formats hold exactly."""
+    os.makedirs(path, exist_ok=True)
+    cols = np.stack([results[k].astype(np.float64) for k in ("res", "status", "dest_len",
+                                                             "src_len")], axis=1)
+    np.save(os.path.join(path, "results.npy"), cols)
+    if nbytes <= DUMP_PIECE * DUMP_PIECES:
+        dec = d_out[:nbytes].cpu().numpy()
+    else:
+        pieces = nbytes // DUMP_PIECE
+        pick = np.sort(np.random.default_rng(0x5EED).choice(pieces, DUMP_PIECES, replace=False))
+        rows = d_out[:pieces * DUMP_PIECE].view(pieces, DUMP_PIECE)
+        dec = rows[torch.from_numpy(pick).to(d_out.device)].cpu().numpy()
+    np.save(os.path.join(path, "decoded.npy"), dec.astype(np.float32))
+    for name, a in (extra or {}).items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a).astype(np.float64))
+
+
 def plan_kernels(plan):
     """Names of the kernels a plan launches (one per LDS class, + the generic one)."""
     names = []
@@ -457,11 +500,75 @@ def run_cfg1(args):
               and (allres["dest_len"] == e_end["dest_len"]).all()
               and (allres["src_len"] == e_end["src_len"]).all())
     ok = ok and sha(d_dst[:n].cpu().numpy().tobytes()) == want_sha
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, d_dst, n, allres[-1])
 
-    # ---- host buffers through the drop-in API (PCIe-inclusive)
+    import native
+    dropin = None
+    if args.full:
+        dropin, ok = cfg1_dropin(L, comp, props, n, exp, want_sha, args.steps, ok)
+    ok = D.all_true(ok, dev)
+
+    cpu = None
+    if rank == 0 and not args.no_cpu_baseline:
+        if native.have_ref():
+            lib, pre, kind = native.ref(), "ref", "reference"
+        else:
+            lib, pre, kind = native.oracle(), "orc", "port"
+        reps, t0 = 0, time.perf_counter()
+        while time.perf_counter() - t0 < 3.0 or reps < 3:
+            r = native.decode(lib, pre, comp, props, n, 1)
+            reps += 1
+        dt = (time.perf_counter() - t0) / reps
+        cpu = {"value": round(n / dt / 1e6, 2), "unit": "MB/s", "cores": 1, "kind": kind,
+               "impl": "the reference's LzmaDecode (LzmaDec.c:972, oracle/_ref/libref_lzma.so, "
+                       "gcc -O2, compiled in place)" if kind == "reference" else
+                       "oracle/lzma_oracle.c restatement",
+               "sample": f"the same 1 MiB stream decoded {reps} times on one core, "
+                         f"{dt * 1e3:.2f} ms per call",
+               "verified": sha(r[4]) == want_sha}
+        if kind == "reference":
+            _, _, out, _, ns = native.dic_decode(lib, pre, comp, props, n, 1 << 14)
+            cpu["DecodeToDic_16K_windows_MBps"] = round(n / (ns * 1e-9) / 1e6, 2)
+    value = world * n * args.steps / elapsed / 1e6
+    alg = len(comp) + 5 + n
+    achieved = alg / (dec_ms * 1e-3) / 1e9
+    if rank == 0:
+        print(json.dumps({
+            "metric": "decompressed MB/s, config 1: one 1 MiB stream (single-stream path)",
+            "value": round(value, 3), "unit": "MB/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic text (1 MiB, seed 1), reference-encoded (tests/golden/cfg1_blob.bin)",
+            "config": {"workload": "1 stream x 1 MiB, lc3/lp0/pb2, 64 KiB dict (BASELINE config 1)",
+                       "compressed_bytes": len(comp),
+                       "kernel_plan": {"kernel": plan_kernels(plan),
+                                       "placement": hex(plan.classes[0].lds_mask)
+                                       if plan.n_classes else None}},
+            "roofline": {"bound": "issue", "priced_against": "hbm", "achieved": round(achieved, 4),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 8), "traffic": None,
+                         "kernel": plan_kernels(plan), "kernel_avg_ms": round(dec_ms, 4),
+                         "alg_bytes_per_launch": alg},
+            "dropin_host_buffers": dropin,
+            "cpu_baseline": cpu, "verified": ok}), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+    if not ok:
+        sys.exit(3)
+
+
+def cfg1_dropin(L, comp, props, n, exp, want_sha, steps, ok):
+    """Config 1's stream over host buffers through the drop-in API (PCIe-
+    inclusive; --full), each call checked against the reference's recorded
+    answers.  Returns (the `dropin_host_buffers` object, ok)."""
+    def sha(b):
+        return hashlib.sha256(b).hexdigest()
+
+    e_end = exp[("lzma", n, 1, None, None)]
     dropin = {}
     t0 = time.perf_counter()
-    k_calls = max(1, min(args.steps, 5))
+    k_calls = max(1, min(steps, 5))
     for _ in range(k_calls):
         r = L.LzmaDecode(comp, props, n, 1)
         ok = ok and (r[0], r[1], r[2], r[3], sha(r[4])) == (
@@ -514,55 +621,7 @@ def run_cfg1(args):
         "d2h_bytes": d2h, "round2_h2d_bytes_would_be": calls * big,
         "note": "dicBufSize 64 MiB, the 1 MiB stream decoded into its start; trace equal "
                 "to the oracle's loop"}
-    ok = D.all_true(ok, dev)
-
-    cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
-        if native.have_ref():
-            lib, pre, kind = native.ref(), "ref", "reference"
-        else:
-            lib, pre, kind = native.oracle(), "orc", "port"
-        reps, t0 = 0, time.perf_counter()
-        while time.perf_counter() - t0 < 3.0 or reps < 3:
-            r = native.decode(lib, pre, comp, props, n, 1)
-            reps += 1
-        dt = (time.perf_counter() - t0) / reps
-        cpu = {"value": round(n / dt / 1e6, 2), "unit": "MB/s", "cores": 1, "kind": kind,
-               "impl": "the reference's LzmaDecode (LzmaDec.c:972, oracle/_ref/libref_lzma.so, "
-                       "gcc -O2, compiled in place)" if kind == "reference" else
-                       "oracle/lzma_oracle.c restatement",
-               "sample": f"the same 1 MiB stream decoded {reps} times on one core, "
-                         f"{dt * 1e3:.2f} ms per call",
-               "verified": sha(r[4]) == want_sha}
-        if kind == "reference":
-            _, _, out, _, ns = native.dic_decode(lib, pre, comp, props, n, 1 << 14)
-            cpu["DecodeToDic_16K_windows_MBps"] = round(n / (ns * 1e-9) / 1e6, 2)
-    value = world * n * args.steps / elapsed / 1e6
-    alg = len(comp) + 5 + n
-    achieved = alg / (dec_ms * 1e-3) / 1e9
-    if rank == 0:
-        print(json.dumps({
-            "metric": "decompressed MB/s, config 1: one 1 MiB stream (single-stream path)",
-            "value": round(value, 3), "unit": "MB/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic text (1 MiB, seed 1), reference-encoded (tests/golden/cfg1_blob.bin)",
-            "config": {"workload": "1 stream x 1 MiB, lc3/lp0/pb2, 64 KiB dict (BASELINE config 1)",
-                       "compressed_bytes": len(comp),
-                       "kernel_plan": {"kernel": plan_kernels(plan),
-                                       "placement": hex(plan.classes[0].lds_mask)
-                                       if plan.n_classes else None}},
-            "roofline": {"bound": "issue", "priced_against": "hbm", "achieved": round(achieved, 4),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 8), "traffic": None,
-                         "kernel": plan_kernels(plan), "kernel_avg_ms": round(dec_ms, 4),
-                         "alg_bytes_per_launch": alg},
-            "dropin_host_buffers": dropin,
-            "cpu_baseline": cpu, "verified": ok}), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    if not ok:
-        sys.exit(3)
+    return dropin, ok
 
 
 # ---------------------------------------------------------------- config 4
@@ -783,6 +842,8 @@ def run_cfg4(args):
     ok = ok and bool(np.array_equal(got, np.array(crc_seq[rank * B:(rank + 1) * B],
                                                   dtype=np.uint32)))
     ok = D.all_true(ok, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, d_dst, doff, res[-1], {"decoded_crc32": got})
 
     cpu = None
     if rank == 0 and not args.no_cpu_baseline:  # after the timed region, any world size
@@ -940,6 +1001,8 @@ def run_cfg5(args):
                                  d_chunks.data_ptr(), d_crc.data_ptr(), sh) == 0
     got = np.frombuffer(d_crc.cpu().numpy().tobytes(), dtype="<u4")
     ok = D.all_true(ok and bool(np.array_equal(got, crcs)), dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, d_dst, total_out, res[-1], {"decoded_crc32": got})
     sliced = None
     if args.sliced:
         def check(rr):
@@ -1257,6 +1320,11 @@ def run_xz(args):
     ok = bool((allres["res"] == 0).all() and (allres["status"] == 1).all() and
               (allres["dest_len"] == np.array(lens)[None, :]).all() and (crc == want).all())
     ok = D.all_true(ok, dev)
+    if rank == 0 and args.dump_outputs:
+        # CRC-64 as (high, low) 32-bit halves: float64 holds each exactly
+        dump_outputs(args.dump_outputs, torch, d_dst, total, allres[-1],
+                     {"decoded_crc64_halves": np.stack([crc >> np.uint64(32),
+                                                        crc & np.uint64(0xFFFFFFFF)], axis=1)})
     comp_bytes = len(xz)
     value = total * world * args.steps / elapsed / 1e6
     alg_dec = comp_bytes + total  # read the file once, write the output once
@@ -1395,11 +1463,15 @@ def run_7z(args):
               and (allres["dest_len"] == np.array([f.unpack_size for f in folders])[None, :]).all()
               and (allres["src_len"] == np.array([f.pack_size for f in folders])[None, :]).all()
               and (crc == want).all())
-    # the C-ABI call end to end once (host buffers: upload, open, decode, CRCs, download)
-    t0 = time.perf_counter()
-    r2, out, fres = L.SzExtract(arc, total, max_files=nf)
-    api_ms = (time.perf_counter() - t0) * 1e3
-    ok = ok and r2 == 0 and not any(fres[:nf])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, d_dst, total, allres[-1], {"file_crc32": crc})
+    api_ms = None
+    if args.full:
+        # the C-ABI call end to end once (host buffers: upload, open, decode, CRCs, download)
+        t0 = time.perf_counter()
+        r2, out, fres = L.SzExtract(arc, total, max_files=nf)
+        api_ms = (time.perf_counter() - t0) * 1e3
+        ok = ok and r2 == 0 and not any(fres[:nf])
     ok = D.all_true(ok, dev)
     comp_bytes = len(arc)
     value = total * world * args.steps / elapsed / 1e6
@@ -1417,7 +1489,8 @@ def run_7z(args):
                        "archive_bytes": comp_bytes, "unpack_bytes": total,
                        "kernel_ms": {"lzma_batch": round(ms[0], 4), "crc32_files": round(ms[1], 4)},
                        "open_ms_host": round(open_ms, 3),
-                       "extract_api_ms_pcie_inclusive": round(api_ms, 3),
+                       "extract_api_ms_pcie_inclusive": None if api_ms is None
+                       else round(api_ms, 3),
                        "parallelism": f"{world} rank(s), one archive each, no collective"},
             "roofline": {"bound": "issue", "priced_against": "hbm", "kernel": f"{plan_kernels(plan)} (7z LZMA folders)",
                          "achieved": round(dec_gbps, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1652,11 +1725,11 @@ def run_coalesce(args):
 def run_secondary(cfgs, steps=5, warmup=1, timeout=420):
     """The other BASELINE configs, each a short run of this script in a child
     process (started, not exec'd: this process has touched the GPU), so the
-    default bench line also carries them.  Not `value`."""
+    --full bench line also carries them.  Not `value`."""
     out = {}
     for c in cfgs:
         cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--steps", str(steps),
-               "--warmup", str(warmup), "--no-cpu-baseline", "--no-e2e", "--no-crc",
+               "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-e2e", "--no-crc",
                "--no-secondary"]
         if c == "cfg2":
             cmd += ["--sliced", "16384"]  # the time-sliced form of the same batch beside it
@@ -1792,6 +1865,12 @@ def main():
     ap.add_argument("--blocks", type=int, default=1024, help="cfg4: LZMA2 blocks per GPU")
     ap.add_argument("--no-gather", action="store_true",
                     help="cfg4: skip the optional gather of decoded blocks on rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: CPU baseline, CRC-32 leg, "
+                         "H2D + decode + D2H, the secondary configs, config 1's drop-in calls, "
+                         "7z's SzExtract call (each --no-* below switches one of them off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-crc", action="store_true", help="skip the CRC-32 (8(f) row 1) leg")
     ap.add_argument("--no-e2e", action="store_true", help="skip the H2D + decode + D2H leg")
@@ -1805,6 +1884,10 @@ def main():
                     help="config 3 at N = 1: skip the short runs of configs 2, 4 and 5 "
                          "reported under 'secondary'")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_crc = args.no_e2e = args.no_secondary = True
     if "RANK" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus)  # spawns the ranks; touches no GPU here
     if args.dry_run:
@@ -1909,6 +1992,11 @@ def main():
         log(f"[rank {rank}] VERIFY FAILED: res={np.unique(allres['res'])} "
             f"status={np.unique(allres['status'])}")
     d_res = d_res_steps[args.steps - 1]
+    if rank == 0 and args.dump_outputs:
+        import zlib
+        rows = out.reshape(count, n)
+        dump_outputs(args.dump_outputs, torch, d_dst, count * n, allres[-1],
+                     {"decoded_crc32": [zlib.crc32(rows[i]) for i in range(count)]})
 
     print_prof(L)
     crc = measure_crc(L, torch, descs, d_desc, d_res, d_dst, plain, count, n, stream, dev,

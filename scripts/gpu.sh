@@ -11,8 +11,8 @@
 #                              liblzmagpu_NAME.so from `make variants`),
 #                              ROUNDS rounds (default 2), interleaved
 #   suite[:VARIANT]            the GPU test suite (on a variant library)
-#   bench[:ARGS]               the default bench line (ARGS: comma-separated
-#                              extra bench.py arguments)
+#   bench[:ARGS]               the whole bench line, bench.py --full (ARGS:
+#                              comma-separated extra bench.py arguments)
 #   profile:CFG[:VARIANT]      kernel trace + separate PMC passes of CFG
 #                              (scripts/profile.sh) -> TAG/prof_CFG
 #   shares:CFG:S1,S2,...[:ENV] bench --streams S of CFG: one GPU's share of a
@@ -66,7 +66,7 @@ for step in "$@"; do
         --timeout 120 --timeout-method thread > "$O/suite_${a:-base}.log" 2>&1
       s=$?; echo "suite ${a:-base} exit $s: $(tail -1 "$O/suite_${a:-base}.log")"; [ $s -eq 0 ] || exit $s ;;
     bench)
-      timeout -k 10 600 python3 bench.py ${a//,/ } > "$O/bench_line.json" 2> "$O/bench.err" || exit $?
+      timeout -k 10 600 python3 bench.py --full ${a//,/ } > "$O/bench_line.json" 2> "$O/bench.err" || exit $?
       echo "bench: $(python3 -c "import json;d=json.load(open('$O/bench_line.json'));print(d['value'], d['ms_per_step'], d['verified'], {k:(v['value'],v['verified']) for k,v in d.get('secondary',{}).items()})")" ;;
     profile)
       LZGPU_LIB=$(lib_abs "$b") bash scripts/profile.sh "$O/prof_$a" --config "$a" || exit $? ;;
