@@ -649,6 +649,39 @@ SRes Crc64Gpu_Batch(const Byte *d_data, const uint64_t *d_off, const uint64_t *d
                     uint64_t init, uint64_t xorout, uint64_t *d_chunk_crc, uint64_t *d_crc,
                     void *stream);
 
+/* SHA-256 (FIPS 180-4), drop-ins for Sha256.h:11-22 (Sha256.c:12-204).  CSha256
+ * has the reference's layout (104 bytes); after every call state, count and
+ * buffer[0 .. count & 63) hold what the reference's hold (Sha256_Final
+ * re-initialises the struct).  Every compression runs on the GPU:
+ * Sha256_Update uploads the buffered bytes plus the whole 64-byte blocks its
+ * data completes and continues from p->state; a call that completes no block
+ * only buffers (no device call); Sha256_Final sends the padded tail.  No error
+ * channel: without a device the calls print once, the state is left as it is
+ * and Sha256_Final writes a zero digest. */
+#define SHA256_DIGEST_SIZE 32
+typedef struct {
+  UInt32 state[8];
+  UInt64 count;
+  Byte buffer[64];
+} CSha256;
+void Sha256_Init(CSha256 *p);
+void Sha256_Update(CSha256 *p, const Byte *data, size_t size);
+void Sha256_Final(CSha256 *p, Byte *digest);
+
+/* Batch form over device ranges: d_digest[32 * i .. + 32) = SHA-256 of
+ * d_data[off[i] .. off[i] + len[i]), any byte alignment, any length (0 too).
+ * kernel: LANE = one lane per range (many ranges), WAVE = one wave per range
+ * (few long ranges: the 64 lanes compute the message schedules of 64
+ * consecutive blocks side by side), AUTO = by n alone, the wave kernel up to
+ * 1,024 ranges (one per SIMD of the chip) and the lane kernel beyond.  All
+ * pointers device memory; asynchronous on `stream`; n == 0 is a no-op.  SZ_ERROR_PARAM: an unknown kernel or n above 2^32 - 1;
+ * SZ_ERROR_FAIL without a device. */
+#define LZMA_GPU_SHA256_AUTO 0
+#define LZMA_GPU_SHA256_LANE 1
+#define LZMA_GPU_SHA256_WAVE 2
+SRes Sha256Gpu_Batch(const Byte *d_data, const uint64_t *d_off, const uint64_t *d_len,
+                     size_t n, unsigned kernel, Byte *d_digest /* n x 32 */, void *stream);
+
 /* xz files as block batches.  The reference decodes xz strictly in order
  * (XzUnpacker_Code, XzDec.c:604-870); the blocks of a multi-block file (and
  * the streams of a concatenated one) are independent, so here the whole file
@@ -656,8 +689,9 @@ SRes Crc64Gpu_Batch(const Byte *d_data, const uint64_t *d_off, const uint64_t *d
  * Xzs_ReadBackward does (XzIn.c:150-280) -- and every block decodes as one
  * lane of an LZMA2 batch, then its filter chain (x86 / PPC / IA64 / ARM /
  * ARMT / SPARC branch converters, delta; last filter first, one batch per
- * kind and depth), then the block checks on the GPU (CRC-32, CRC-64;
- * SHA-256 on the host). */
+ * kind and depth), then the block checks on the GPU (CRC-32, CRC-64 and
+ * SHA-256, one batch each over the decode's own buffers; the host only
+ * compares the results with the stored check fields). */
 #define LZMA_GPU_XZ_CHECK_NONE 0
 #define LZMA_GPU_XZ_CHECK_CRC32 1
 #define LZMA_GPU_XZ_CHECK_CRC64 4
@@ -709,8 +743,9 @@ SRes LzmaGpu_XzDecode(Byte *dest, SizeT *destLen, const Byte *file, size_t size,
  * and ARM folders go through the branch-converter kernels and every folder /
  * file CRC through one CRC-32 batch.  Folder shapes: Copy / LZMA / LZMA2,
  * optionally followed by BCJ x86 or ARM (CheckSupportedFolder, 7zDec.c:269;
- * ARM_Convert at ip 0, :449); BCJ2 folders, which the reference also
- * decodes, return SZ_ERROR_UNSUPPORTED here. */
+ * ARM_Convert at ip 0, :449), and the reference's BCJ2 folder (four coders
+ * in the one bind layout 7zDec.c:303-319 accepts): its three LZMA / LZMA2 /
+ * Copy coders decode in the same batch and Bcj2Gpu_Batch merges them. */
 typedef struct LzmaGpu7zFolder {   /* 80 bytes */
   uint64_t pack_off;     /* archive offset of the main coder's pack stream */
   uint64_t pack_size;

@@ -64,6 +64,30 @@ extern "C" int lzgpu_launch_bcj2(const Bcj2GpuJob* d_jobs, uint32_t n, int32_t* 
 extern "C" int lzgpu_launch_delta(uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
                                   const uint32_t* d_delta, uint8_t* d_state, uint32_t n,
                                   int encoding, hipStream_t stream);
+// SHA-256 of n device ranges d_data[off[i] .. off[i] + len[i]) (sha256_kernels.hip),
+// the one launcher behind Sha256Gpu_Batch, the Sha256.h drop-ins and the xz
+// block check.  Range i continues from the chaining state d_init[8 * i .. + 8)
+// (null: the initial value) with d_prior[i] bytes already hashed (null: 0; they
+// count in the length field).  finalise != 0: the range is padded and
+// d_out[32 * i .. + 32) is its digest; finalise == 0: only its whole 64-byte
+// blocks are hashed and d_out holds the eight state words as uint32.
+// kernel: lane per range, wave per range, or by n alone (lengths live on the
+// device).  0 on success, -2 for an unknown kernel, -1 if the launch failed.
+constexpr unsigned kLzgpuSha256Auto = 0, kLzgpuSha256Lane = 1, kLzgpuSha256Wave = 2;
+// AUTO takes the lane kernel from this many ranges on: more ranges than the
+// chip has SIMDs (256 CUs x 4).  Measured with 1 MiB ranges
+// (profiles/sha256/crossover.jsonl): up to 1,024 ranges every wave of the wave
+// kernel has a SIMD to itself and a range takes 29.4-29.7 ms against the lane
+// kernel's 46.6-51.2 ms; a second wave on a SIMD doubles that (2,048 ranges:
+// 56.2 ms, lane 48.8 ms; 4,096: 136 ms, lane 48.9 ms), while the lane kernel's
+// time stays flat to 16,384 ranges (49.0 ms).  Not measured between 1,024 and
+// 2,048: there some SIMDs already hold two waves, so the batch takes the
+// two-wave time.
+constexpr uint32_t kLzgpuSha256AutoLaneMin = 1025;
+extern "C" int lzgpu_launch_sha256(const uint8_t* d_data, const uint64_t* d_off,
+                                   const uint64_t* d_len, uint32_t n, const uint32_t* d_init,
+                                   const uint64_t* d_prior, int finalise, unsigned kernel,
+                                   uint8_t* d_out, hipStream_t stream);
 
 // host-side helpers shared by the C-ABI translation units (lzma_capi.hip)
 namespace lzgpu_host {

@@ -1,4 +1,5 @@
-// xz_capi.hip -- host side of the xz block batch, x86 BCJ and CRC-64 C ABI
+// xz_capi.hip -- host side of the xz block batch, x86 BCJ, CRC-64 and SHA-256
+// C ABI
 // (include/lzma_gpu.h).
 //
 // The reference reads xz strictly forward (XzUnpacker_Code, XzDec.c:604-870)
@@ -6,10 +7,11 @@
 // Here the backward index is the plan: every block of every stream becomes
 // one LZMA2 item of a single GPU batch (LzmaGpu_PlanBatchEx /
 // LzmaGpu_DecodeBatchEx), followed by the x86 BCJ kernel for blocks that
-// carry the filter and the CRC-32 / CRC-64 kernels for the block checks.
+// carry the filter and the CRC-32 / CRC-64 / SHA-256 kernels for the block
+// checks.
 // The host keeps what the reference keeps outside its coders: container
 // parsing with its small CRC-32s (stream header, block headers, index,
-// footer) and SHA-256 checks.
+// footer) and the comparison of the computed checks with the stored fields.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,82 +52,6 @@ unsigned read_varint(const Byte* p, size_t max, uint64_t* v) {
 
 // XzFlags_GetCheckSize (Xz.c:40-44)
 uint32_t check_size(uint32_t t) { return t == 0 ? 0 : (4u << ((t - 1) / 3)); }
-
-// FIPS 180-4 SHA-256 (the XZ_CHECK_SHA256 block check, Sha256.c)
-struct Sha256 {
-  uint32_t h[8];
-  uint64_t n = 0;
-  Byte buf[64];
-  size_t fill = 0;
-  static uint32_t rotr(uint32_t x, int r) { return (x >> r) | (x << (32 - r)); }
-  Sha256() {
-    static const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
-                                   0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-    memcpy(h, iv, sizeof h);
-  }
-  void block(const Byte* p) {
-    static const uint32_t k[64] = {
-        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4,
-        0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe,
-        0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f,
-        0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7,
-        0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc,
-        0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b,
-        0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116,
-        0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-        0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7,
-        0xc67178f2};
-    uint32_t w[64];
-    for (int i = 0; i < 16; ++i)
-      w[i] = (uint32_t(p[4 * i]) << 24) | (uint32_t(p[4 * i + 1]) << 16) |
-             (uint32_t(p[4 * i + 2]) << 8) | p[4 * i + 3];
-    for (int i = 16; i < 64; ++i) {
-      const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3);
-      const uint32_t s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-      w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-    }
-    uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-    for (int i = 0; i < 64; ++i) {
-      const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) +
-                          k[i] + w[i];
-      const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-      hh = g;
-      g = f;
-      f = e;
-      e = d + t1;
-      d = c;
-      c = b;
-      b = a;
-      a = t1 + t2;
-    }
-    h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-  }
-  void update(const Byte* p, size_t len) {
-    n += len;
-    while (len) {
-      const size_t take = std::min(len, 64 - fill);
-      memcpy(buf + fill, p, take);
-      fill += take;
-      p += take;
-      len -= take;
-      if (fill == 64) {
-        block(buf);
-        fill = 0;
-      }
-    }
-  }
-  void final(Byte* out) {
-    const uint64_t bits = n * 8;
-    const Byte one = 0x80, zero = 0;
-    update(&one, 1);
-    while (fill != 56) update(&zero, 1);
-    Byte l[8];
-    for (int i = 0; i < 8; ++i) l[i] = Byte(bits >> (56 - 8 * i));
-    update(l, 8);
-    for (int i = 0; i < 8; ++i)
-      for (int j = 0; j < 4; ++j) out[4 * i + j] = Byte(h[i] >> (24 - 8 * j));
-  }
-};
 
 // One stream, read backwards from the footer ending at `end` (Xz_ReadBackward,
 // XzIn.c:141-224); blocks appended in stream order; *start = stream start.
@@ -588,6 +514,123 @@ UInt64 Crc64Calc(const void* data, size_t size) {
   return out;
 }
 
+// ---- SHA-256 C ABI: the Sha256.h drop-ins over host buffers and the batch
+// form over device ranges.  No compression function lives on the host: it
+// buffers bytes until a block is complete, as Sha256_Update does
+// (Sha256.c:160-174), and every block, the padding blocks included, is
+// compressed by lzgpu_launch_sha256 (sha256_kernels.hip).
+static_assert(sizeof(CSha256) == 104, "CSha256 layout (Sha256.h:13-18)");
+
+// The kernels' translation unit is part of the library.  A host-only link of
+// the container parsers that leaves it out (the sanitizer build of
+// tests/fuzz/) still links: the reference is weak, and a call without the
+// kernels is an error, never a host computation.
+extern "C" __attribute__((weak)) int lzgpu_launch_sha256(
+    const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len, uint32_t n,
+    const uint32_t* d_init, const uint64_t* d_prior, int finalise, unsigned kernel,
+    uint8_t* d_out, hipStream_t stream);
+
+static int sha256_launch(const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
+                         uint32_t n, const uint32_t* d_init, const uint64_t* d_prior,
+                         int finalise, unsigned kernel, uint8_t* d_out, hipStream_t stream) {
+  if (!lzgpu_launch_sha256) return -3;
+  return lzgpu_launch_sha256(d_data, d_off, d_len, n, d_init, d_prior, finalise, kernel, d_out,
+                             stream);
+}
+
+SRes Sha256Gpu_Batch(const Byte* d_data, const uint64_t* d_off, const uint64_t* d_len, size_t n,
+                     unsigned kernel, Byte* d_digest, void* stream) {
+  if (kernel > LZMA_GPU_SHA256_WAVE || n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
+  if (!ensure_device()) return SZ_ERROR_FAIL;
+  if (sha256_launch(d_data, d_off, d_len, uint32_t(n), nullptr, nullptr, 1, kernel,
+                          d_digest, static_cast<hipStream_t>(stream)) != 0) {
+    set_error("SHA-256 kernel launch failed");
+    return SZ_ERROR_FAIL;
+  }
+  return SZ_OK;
+}
+
+namespace {
+
+// One range on the device: head (the bytes buffered in the struct) followed by
+// body, continued from `state` with `prior` bytes hashed before.  finalise:
+// out = the 32 digest bytes; else out = the state after the whole blocks.
+// One message is one serial chain: the wave kernel.
+bool sha256_host_range(const uint32_t state[8], uint64_t prior, const Byte* head, size_t n_head,
+                       const Byte* body, size_t n_body, int finalise, void* out) {
+  lzgpu_host::CallScratch* S = lzgpu_host::scratch_acquire();
+  if (!S) return false;
+  const size_t size = n_head + n_body;
+  // one upload: [offset, length, prior | state | 32 bytes of result]
+  uint64_t meta[3 + 4] = {0, uint64_t(size), prior};
+  memcpy(meta + 3, state, 32);
+  uint8_t* d_data = static_cast<uint8_t*>(S->buf[0].get(size));
+  uint8_t* d_meta = static_cast<uint8_t*>(S->buf[1].get(sizeof meta + 32));
+  const hipStream_t st = S->stream;
+  bool ok = false;
+  if (!d_data || !d_meta) {
+    set_error("SHA-256: device allocation failed");
+  } else {
+    uint64_t* d_m = reinterpret_cast<uint64_t*>(d_meta);
+    ok = (n_head == 0 ||
+          hip_ok(hipMemcpyAsync(d_data, head, n_head, hipMemcpyHostToDevice, st), "SHA-256 H2D")) &&
+         (n_body == 0 || hip_ok(hipMemcpyAsync(d_data + n_head, body, n_body,
+                                               hipMemcpyHostToDevice, st),
+                                "SHA-256 H2D")) &&
+         hip_ok(hipMemcpyAsync(d_meta, meta, sizeof meta, hipMemcpyHostToDevice, st),
+                "SHA-256 H2D");
+    if (ok && sha256_launch(d_data, d_m, d_m + 1, 1, reinterpret_cast<uint32_t*>(d_m + 3),
+                                  d_m + 2, finalise, kLzgpuSha256Wave, d_meta + sizeof meta,
+                                  st) != 0) {
+      set_error("SHA-256 kernel launch failed");
+      ok = false;
+    }
+    ok = ok &&
+         hip_ok(hipMemcpyAsync(out, d_meta + sizeof meta, 32, hipMemcpyDeviceToHost, st),
+                "SHA-256 D2H") &&
+         hip_ok(hipStreamSynchronize(st), "SHA-256 kernel");
+  }
+  (void)hipStreamSynchronize(st);  // host buffers are reused after return
+  lzgpu_host::scratch_release(S);
+  return ok;
+}
+
+}  // namespace
+
+void Sha256_Init(CSha256* p) {
+  static const UInt32 iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                               0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  memcpy(p->state, iv, sizeof iv);
+  p->count = 0;
+}
+
+void Sha256_Update(CSha256* p, const Byte* data, size_t size) {
+  const size_t fill = size_t(p->count & 0x3F);
+  if (size < 64 - fill) {  // no block completes: buffer only
+    if (size) memcpy(p->buffer + fill, data, size);
+    p->count += size;
+    return;
+  }
+  // the buffered bytes and the data up to the last block boundary go to the
+  // device; what is left over becomes the new buffer contents
+  const size_t whole = ((fill + size) & ~size_t(63)) - fill, rest = size - whole;
+  if (ensure_device()) {
+    UInt32 st[8];
+    if (sha256_host_range(p->state, p->count - fill, p->buffer, fill, data, whole, 0, st))
+      memcpy(p->state, st, sizeof st);
+  }
+  if (rest) memcpy(p->buffer, data + whole, rest);
+  p->count += size;
+}
+
+void Sha256_Final(CSha256* p, Byte* digest) {
+  const size_t fill = size_t(p->count & 0x3F);
+  if (!ensure_device() ||
+      !sha256_host_range(p->state, p->count - fill, p->buffer, fill, nullptr, 0, 1, digest))
+    memset(digest, 0, SHA256_DIGEST_SIZE);
+  Sha256_Init(p);
+}
+
 static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
                       int64_t* bad_block) {
   const SizeT cap = *destLen;
@@ -624,9 +667,10 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
   std::vector<uint32_t> order(n);
   LzmaGpuPlan plan;
   if ((r = LzmaGpu_PlanBatchEx(descs.data(), n, order.data(), &plan)) != SZ_OK) return r;
-  // check ranges (after BCJ): CRC-32 and CRC-64 blocks, chunk plans
-  std::vector<uint64_t> off32, len32, off64, len64;
-  std::vector<size_t> idx32, idx64;
+  // check ranges (after the filters): CRC-32, CRC-64 and SHA-256 blocks, chunk
+  // plans for the CRCs
+  std::vector<uint64_t> off32, len32, off64, len64, offsha, lensha;
+  std::vector<size_t> idx32, idx64, idxsha;
   for (size_t i = 0; i < n; ++i) {
     if (blk[i].check_type == LZMA_GPU_XZ_CHECK_CRC32) {
       idx32.push_back(i);
@@ -636,6 +680,10 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
       idx64.push_back(i);
       off64.push_back(blk[i].dst_off);
       len64.push_back(blk[i].unpack_size);
+    } else if (blk[i].check_type == LZMA_GPU_XZ_CHECK_SHA256) {
+      idxsha.push_back(i);
+      offsha.push_back(blk[i].dst_off);
+      lensha.push_back(blk[i].unpack_size);
     }
   }
   const size_t nch32 = CrcGpu_PlanChunks(len32.data(), len32.size(), nullptr, nullptr);
@@ -649,27 +697,31 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
   DevArr<LzmaGpuStreamDesc> d_desc;
   DevArr<uint32_t> d_order, d_cb32, d_cb64, d_crc32, d_chunk32;
   DevArr<LzmaGpuResult> d_res;
-  DevArr<uint64_t> d_ol32, d_ol64, d_chunk64, d_crc64;
+  DevArr<uint64_t> d_ol32, d_ol64, d_chunk64, d_crc64, d_olsha;
+  DevArr<Byte> d_sha;
   if (!d_src.alloc(size) || !d_dst.alloc(total) || !d_ws.alloc(plan.workspace_bytes) ||
       !d_desc.alloc(n) || !d_order.alloc(n) || !d_res.alloc(n) ||
       !d_ol32.alloc(2 * off32.size()) || !d_cb32.alloc(cb32.size()) ||
       !d_chunk32.alloc(nch32) || !d_crc32.alloc(off32.size()) ||
       !d_ol64.alloc(2 * off64.size()) || !d_cb64.alloc(cb64.size()) ||
-      !d_chunk64.alloc(nch64) || !d_crc64.alloc(off64.size())) {
+      !d_chunk64.alloc(nch64) || !d_crc64.alloc(off64.size()) ||
+      !d_olsha.alloc(2 * offsha.size()) || !d_sha.alloc(32 * offsha.size())) {
     set_error("XzDecode: device allocation failed");
     return SZ_ERROR_MEM;
   }
   auto h2d = [](void* d, const void* h, size_t bytes) {
     return bytes == 0 || hip_ok(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice), "XzDecode H2D");
   };
-  std::vector<uint64_t> ol32(off32), ol64(off64);
+  std::vector<uint64_t> ol32(off32), ol64(off64), olsha(offsha);
   ol32.insert(ol32.end(), len32.begin(), len32.end());
   ol64.insert(ol64.end(), len64.begin(), len64.end());
+  olsha.insert(olsha.end(), lensha.begin(), lensha.end());
   if (!h2d(d_src.p, file, size) || !h2d(d_desc.p, descs.data(), n * sizeof(LzmaGpuStreamDesc)) ||
       !h2d(d_order.p, order.data(), n * 4) || !h2d(d_ol32.p, ol32.data(), ol32.size() * 8) ||
       !h2d(d_cb32.p, cb32.data(), cb32.size() * 4) ||
       !h2d(d_ol64.p, ol64.data(), ol64.size() * 8) ||
-      !h2d(d_cb64.p, cb64.data(), cb64.size() * 4))
+      !h2d(d_cb64.p, cb64.data(), cb64.size() * 4) ||
+      !h2d(d_olsha.p, olsha.data(), olsha.size() * 8))
     return SZ_ERROR_FAIL;
   if ((r = LzmaGpu_DecodeBatchEx(&plan, d_desc.p, d_order.p, d_src.p, d_dst.p, d_ws.p, d_res.p,
                                  nullptr)) != SZ_OK)
@@ -714,7 +766,7 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
       if (!hip_ok(hipDeviceSynchronize(), "XzDecode filters")) return SZ_ERROR_FAIL;
     }
   }
-  const size_t n32 = off32.size(), n64 = off64.size();
+  const size_t n32 = off32.size(), n64 = off64.size(), nsha = offsha.size();
   if (n32 && (r = CrcGpu_Batch(d_dst.p, d_ol32.p, d_ol32.p + n32, n32, d_cb32.p, d_cb32.p + n32,
                                nch32, 0xFFFFFFFFu, 0xFFFFFFFFu, d_chunk32.p, d_crc32.p,
                                nullptr)) != SZ_OK)
@@ -722,9 +774,13 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
   if (n64 && (r = Crc64Gpu_Batch(d_dst.p, d_ol64.p, d_ol64.p + n64, n64, d_cb64.p, d_cb64.p + n64,
                                  nch64, ~0ull, ~0ull, d_chunk64.p, d_crc64.p, nullptr)) != SZ_OK)
     return r;
+  if (nsha && (r = Sha256Gpu_Batch(d_dst.p, d_olsha.p, d_olsha.p + nsha, nsha,
+                                   LZMA_GPU_SHA256_AUTO, d_sha.p, nullptr)) != SZ_OK)
+    return r;
   std::vector<LzmaGpuResult> res(n);
   std::vector<uint32_t> crc32(n32);
   std::vector<uint64_t> crc64(n64);
+  std::vector<Byte> sha(32 * nsha);
   if (!hip_ok(hipDeviceSynchronize(), "XzDecode kernels") ||
       !hip_ok(hipMemcpy(res.data(), d_res.p, n * sizeof(LzmaGpuResult), hipMemcpyDeviceToHost),
               "XzDecode D2H") ||
@@ -732,6 +788,8 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
                       "XzDecode D2H")) ||
       (n64 && !hip_ok(hipMemcpy(crc64.data(), d_crc64.p, n64 * 8, hipMemcpyDeviceToHost),
                       "XzDecode D2H")) ||
+      (nsha && !hip_ok(hipMemcpy(sha.data(), d_sha.p, 32 * nsha, hipMemcpyDeviceToHost),
+                       "XzDecode D2H")) ||
       !hip_ok(hipMemcpy(dest, d_dst.p, total, hipMemcpyDeviceToHost), "XzDecode D2H"))
     return SZ_ERROR_FAIL;
   for (size_t i = 0; i < n; ++i) {
@@ -750,14 +808,11 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
                           (uint64_t(le32(file + blk[i].check_off + 4)) << 32);
     if (fail[i] == SZ_OK && crc64[k] != want) fail[i] = SZ_ERROR_CRC;
   }
-  for (size_t i = 0; i < n; ++i)
-    if (fail[i] == SZ_OK && blk[i].check_type == LZMA_GPU_XZ_CHECK_SHA256) {
-      Sha256 h;
-      Byte dig[32];
-      h.update(dest + blk[i].dst_off, size_t(blk[i].unpack_size));
-      h.final(dig);
-      if (memcmp(dig, file + blk[i].check_off, 32) != 0) fail[i] = SZ_ERROR_CRC;
-    }
+  for (size_t k = 0; k < nsha; ++k) {
+    const size_t i = idxsha[k];
+    if (fail[i] == SZ_OK && memcmp(&sha[32 * k], file + blk[i].check_off, 32) != 0)
+      fail[i] = SZ_ERROR_CRC;
+  }
   for (size_t i = 0; i < n; ++i)
     if (fail[i] != SZ_OK) {
       if (bad_block) *bad_block = int64_t(i);

@@ -163,6 +163,12 @@ class Bcj2Job(ctypes.Structure):
                 ("out_size", ctypes.c_uint64)]
 
 
+class CSha256(ctypes.Structure):
+    """CSha256 (Sha256.h:13-18): the drop-in hash state, the reference's layout."""
+    _fields_ = [("state", ctypes.c_uint32 * 8), ("count", ctypes.c_uint64),
+                ("buffer", ctypes.c_ubyte * 64)]
+
+
 class SzFolder(ctypes.Structure):
     """LzmaGpu7zFolder (include/lzma_gpu.h): one folder of an opened 7z archive."""
     _fields_ = [("pack_off", ctypes.c_uint64), ("pack_size", ctypes.c_uint64),
@@ -189,6 +195,7 @@ assert ctypes.sizeof(StreamDesc) == 48 and ctypes.sizeof(Result) == 24
 assert ctypes.sizeof(Session) == 192 and ctypes.sizeof(Plan) == 248
 assert ctypes.sizeof(PlanOptions) == 40
 assert ctypes.sizeof(CLzmaDec) == 136
+assert ctypes.sizeof(CSha256) == 104
 
 _P = ctypes.c_void_p
 _sig = {
@@ -250,6 +257,10 @@ _sig = {
     "Bcj2Gpu_Batch": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P]),
     "Crc64Calc": (ctypes.c_uint64, [_P, ctypes.c_size_t]),
     "Crc64Gpu_Batch": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P]),
+    "Sha256_Init": (None, [ctypes.POINTER(CSha256)]),
+    "Sha256_Update": (None, [ctypes.POINTER(CSha256), _P, ctypes.c_size_t]),
+    "Sha256_Final": (None, [ctypes.POINTER(CSha256), _P]),
+    "Sha256Gpu_Batch": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, ctypes.c_uint, _P, _P]),
     "LzmaGpu_XzIndex": (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.POINTER(XzBlock), ctypes.c_size_t, _sp, ctypes.POINTER(ctypes.c_uint64)]),
     "LzmaGpu_XzDecode": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]),
     "LzmaGpu_7zOpen": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _sp, _P,
@@ -690,6 +701,40 @@ def crc64_batch_device(d_data, d_off, d_len, n, d_base, d_range, n_chunks, init,
     """Crc64Gpu_Batch over raw device pointers (ints)."""
     return _lib.Crc64Gpu_Batch(d_data, d_off, d_len, n, d_base, d_range, n_chunks, init, xorout,
                                d_chunk_crc, d_crc, stream or None)
+
+
+SHA256_DIGEST_SIZE = 32
+SHA256_AUTO, SHA256_LANE, SHA256_WAVE = 0, 1, 2  # LZMA_GPU_SHA256_*
+
+
+def Sha256_Init(p):
+    """Sha256.c Sha256_Init on a CSha256."""
+    _lib.Sha256_Init(ctypes.byref(p))
+
+
+def Sha256_Update(p, data):
+    """Sha256.c Sha256_Update: whole blocks are compressed on the GPU, the rest buffered."""
+    _lib.Sha256_Update(ctypes.byref(p), _buf(data), len(data))
+
+
+def Sha256_Final(p):
+    """Sha256.c Sha256_Final: the 32 digest bytes; p is re-initialised."""
+    out = ctypes.create_string_buffer(SHA256_DIGEST_SIZE)
+    _lib.Sha256_Final(ctypes.byref(p), out)
+    return out.raw
+
+
+def Sha256(data):
+    """SHA-256 of a host buffer through the drop-ins (GPU compute)."""
+    p = CSha256()
+    Sha256_Init(p)
+    Sha256_Update(p, data)
+    return Sha256_Final(p)
+
+
+def sha256_batch_device(d_data, d_off, d_len, n, d_digest, kernel=SHA256_AUTO, stream=0):
+    """Sha256Gpu_Batch over raw device pointers (ints); d_digest: n x 32 bytes."""
+    return _lib.Sha256Gpu_Batch(d_data, d_off, d_len, n, kernel, d_digest, stream or None)
 
 
 def xz_index(data):
