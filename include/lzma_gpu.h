@@ -735,6 +735,70 @@ SRes LzmaGpu_XzIndex(const Byte *file, size_t size, LzmaGpuXzBlock *blocks, size
 SRes LzmaGpu_XzDecode(Byte *dest, SizeT *destLen, const Byte *file, size_t size,
                       int64_t *bad_block);
 
+/* ---------------------------------------------------------------- PPMd7 (PPMdH) batches */
+
+/* Ppmd7.c + Ppmd7Dec.c on the GPU: the reference's model, sub-allocator and 7z
+ * range decoder, one stream per wave, many independent streams per launch.
+ * Per stream the outcome is SzDecodePpmd's (7zDec.c:66-122) over a memory
+ * buffer of exactly src_len bytes, checked in this order:
+ *   order outside 2..64 or mem_size outside 1<<11 .. 0xFFFFFFFF-36
+ *                                  SZ_ERROR_UNSUPPORTED, nothing read or written
+ *   first byte non-zero, or Code == 0xFFFFFFFF after the 5 init bytes
+ *                                  SZ_ERROR_DATA
+ *   a read past src_len (it returns 0 and sets the reference's `extra` flag,
+ *   tested after the init bytes and after each symbol)   SZ_ERROR_DATA
+ *   a negative symbol              SZ_ERROR_DATA
+ *   after dst_len symbols: bytes consumed != src_len, or Code != 0
+ *                                  SZ_ERROR_DATA
+ *   else                           SZ_OK
+ * dest_len = symbols written before the loop stopped, src_len = bytes consumed
+ * (at most the descriptor's).  Bytes of d_dst outside
+ * [dst_off, dst_off + dest_len) are not written. */
+#define LZMA_GPU_PPMD7_PROPS_SIZE 5  /* order byte, memSize LE32: the 7z coder props */
+
+/* One stream of a batch (48 bytes).  Offsets index the caller's packed device
+ * buffers; any byte alignment for src_off / dst_off.  ws_off: the stream's own
+ * slice of the workspace, Ppmd7Gpu_WorkspaceBytes(mem_size) bytes at a multiple
+ * of 256 (slices must not overlap; their contents need no initialisation). */
+typedef struct Ppmd7GpuStreamDesc {
+  uint64_t src_off;   /* packed bytes start in d_src */
+  uint64_t src_len;   /* packed bytes (inSize) */
+  uint64_t dst_off;   /* output start in d_dst */
+  uint64_t dst_len;   /* symbols to decode (outSize) */
+  uint64_t ws_off;    /* slice start in d_workspace, bytes */
+  uint32_t mem_size;  /* props[1..5), little endian */
+  uint32_t order;     /* props[0] */
+} Ppmd7GpuStreamDesc;
+
+/* Per-stream outcome (24 bytes). */
+typedef struct Ppmd7GpuResult {
+  int32_t res;
+  uint32_t _pad;
+  uint64_t dest_len;
+  uint64_t src_len;
+} Ppmd7GpuResult;
+
+/* One stream's workspace slice in bytes, a multiple of 256: the model
+ * (mem_size plus the reference's alignment offset and list head) and its
+ * BinSumm table.  0 for a mem_size outside the range above. */
+uint64_t Ppmd7Gpu_WorkspaceBytes(uint32_t mem_size);
+/* Decode n streams on the current device, one workgroup of one wave each, in
+ * index order (put long streams first).  All pointers are device memory owned
+ * by the caller; asynchronous on `stream`; n == 0 is a no-op.  Returns SZ_OK
+ * if the launch was queued (SZ_ERROR_FAIL without a device, SZ_ERROR_PARAM for
+ * n above 2^31 - 1); per-stream outcomes land in d_results. */
+SRes Ppmd7Gpu_DecodeBatch(const Ppmd7GpuStreamDesc *d_descs, size_t n, const Byte *d_src,
+                          Byte *d_dst, void *d_workspace, Ppmd7GpuResult *d_results, void *stream);
+/* The same over host buffers: stages src and dst, lays the slices out itself
+ * (descs[i].ws_off is ignored), orders the streams longest first and decodes in
+ * as many launches as keep the workspace at or under workspace_limit bytes
+ * (0 = half of the device's free memory).  SZ_ERROR_MEM if one stream's slice
+ * alone exceeds the limit or an allocation fails, SZ_ERROR_PARAM for a range
+ * outside src / dst, SZ_ERROR_FAIL without a device. */
+SRes Ppmd7Gpu_DecodeBatchHost(const Ppmd7GpuStreamDesc *descs, size_t n, const Byte *src,
+                              size_t src_size, Byte *dst, size_t dst_size,
+                              Ppmd7GpuResult *results, uint64_t workspace_limit);
+
 /* ---- 7z archives as folder batches ----------------
  * Replaces SzArEx_Open (7zIn.c:1314) + a SzArEx_Extract loop over every file
  * (7zIn.c:1322; ExtractAllFiles 7zIn.c:1405 in the fork): the header walk
@@ -789,6 +853,25 @@ SRes LzmaGpu_7zOpen(const Byte *archive, size_t size, LzmaGpu7zFolder *folders,
  * first file's non-OK result, else SZ_OK. */
 SRes LzmaGpu_7zExtract(Byte *dest, SizeT *destLen, const Byte *archive, size_t size,
                        SRes *file_res, size_t file_cap);
+
+/* The same with options.  flags = 0: exactly the two calls above.
+ * LZMA_GPU_7Z_PPMD: method 0x030401 (PPMd7, the reference's compile-time
+ * _7ZIP_PPMD_SUPPPORT, 7zDec.c:29-124, here a run-time choice) is a main
+ * method wherever Copy / LZMA / LZMA2 are in the 1- and 2-coder shapes: alone
+ * and under the x86 or ARM filter, in folders and in a packed header.  Its
+ * checks before decoding are SzDecodePpmd's (props size != 5, order or memSize
+ * out of range: SZ_ERROR_UNSUPPORTED); its streams decode in one
+ * Ppmd7Gpu_DecodeBatch beside the LZMA batch.  Deviation from the reference's
+ * switch: a PPMd coder inside a BCJ2 folder stays SZ_ERROR_UNSUPPORTED.  A flag
+ * bit outside LZMA_GPU_7Z_KNOWN_FLAGS: SZ_ERROR_PARAM. */
+#define LZMA_GPU_7Z_PPMD 1u
+#define LZMA_GPU_7Z_KNOWN_FLAGS 1u
+SRes LzmaGpu_7zOpenEx(const Byte *archive, size_t size, LzmaGpu7zFolder *folders,
+                      size_t folder_cap, size_t *n_folders, LzmaGpu7zFile *files, size_t file_cap,
+                      size_t *n_files, UInt16 *names, size_t names_cap, size_t *names_len,
+                      UInt64 *unpack_total, unsigned flags);
+SRes LzmaGpu_7zExtractEx(Byte *dest, SizeT *destLen, const Byte *archive, size_t size,
+                         SRes *file_res, size_t file_cap, unsigned flags);
 
 /* Device / diagnostics. */
 int LzmaGpu_DeviceCount(void);

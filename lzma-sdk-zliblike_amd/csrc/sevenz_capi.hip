@@ -12,6 +12,13 @@
 // folders as device copies, then the x86 BCJ kernel over BCJ folders and one
 // CRC-32 batch over every folder and file range.  Per-file results are what
 // SzArEx_Extract returns for that file with a fresh folder cache.
+//
+// PPMd (method 0x030401, SzDecodePpmd 7zDec.c:29-124) is a compile-time switch
+// of the reference (_7ZIP_PPMD_SUPPPORT) and a run-time flag here
+// (LZMA_GPU_7Z_PPMD of the Ex entry points; off = the reference as built):
+// its coders run as one Ppmd7Gpu_DecodeBatch beside the LZMA batch.  Deviation
+// from the reference's switch: a PPMd coder inside a BCJ2 folder stays
+// SZ_ERROR_UNSUPPORTED with the flag.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +28,7 @@
 #include <vector>
 
 #include "lzma_gpu_internal.h"
+#include "ppmd7_internal.h"
 
 using lzgpu_host::crc32_host;
 using lzgpu_host::DevArr;
@@ -39,7 +47,7 @@ enum : uint64_t {
 };
 // coder ids (7zDec.c:19-31)
 constexpr uint64_t kCopy = 0, kLzma = 0x30101, kLzma2 = 0x21, kBcj = 0x03030103,
-                   kArm = 0x03030501, kBcj2 = 0x0303011B;
+                   kArm = 0x03030501, kBcj2 = 0x0303011B, kPpmd = 0x30401;
 constexpr size_t kStartHeader = 32;
 constexpr uint32_t kNoFolder = 0xFFFFFFFFu;
 
@@ -111,6 +119,7 @@ struct Archive {
   std::vector<size_t> name_offsets;  // FileNameOffsets (UTF-16 units), numFiles + 1
   std::vector<uint32_t> folder_start_pack, folder_start_file, file_folder;
   std::vector<uint64_t> pack_start;
+  unsigned flags = 0;  // LZMA_GPU_7Z_*
 };
 
 // CSzData readers (7zIn.c:310-400)
@@ -641,6 +650,17 @@ static void unit_checks(Unit& u) {
   } else if (u.method == kLzma) {
     // LzmaProps_Decode (LzmaDec.c:898-922)
     if (u.props.size() < 5 || u.props[0] >= 9 * 5 * 5) u.pre = SZ_ERROR_UNSUPPORTED;
+  } else if (u.method == kPpmd) {
+    // SzDecodePpmd (7zDec.c:80-90)
+    if (u.props.size() != LZMA_GPU_PPMD7_PROPS_SIZE) {
+      u.pre = SZ_ERROR_UNSUPPORTED;
+    } else {
+      const uint32_t order = u.props[0];
+      const uint32_t mem = u.props[1] | (u.props[2] << 8) | (u.props[3] << 16) |
+                           (uint32_t(u.props[4]) << 24);
+      if (order < 2 || order > 64 || mem < (1u << 11) || mem > 0xFFFFFFFFu - 36u)
+        u.pre = SZ_ERROR_UNSUPPORTED;
+    }
   } else {
     // SzDecodeLzma2 (7zDec.c:181-183) + Lzma2Dec_GetOldProps (Lzma2Dec.c:69)
     if (u.props.size() != 1) u.pre = SZ_ERROR_DATA;
@@ -653,13 +673,17 @@ Job make_job(const Archive& x, const Ar& a, uint32_t fi, uint64_t start, const B
   Job j;
   const Folder& f = a.folders[fi];
   j.unpack = f.unpack_size();
-  auto main_ok = [](const Coder& c) {
+  // PPMd (LZMA_GPU_7Z_PPMD) is a main method of the 1- and 2-coder shapes only:
+  // inside a BCJ2 folder it stays unsupported
+  auto main_ok = [](const Coder& c, bool ppmd = false) {
     return c.nin == 1 && c.nout == 1 && c.method <= 0xFFFFFFFFull &&
-           (c.method == kCopy || c.method == kLzma || c.method == kLzma2);
+           (c.method == kCopy || c.method == kLzma || c.method == kLzma2 ||
+            (ppmd && c.method == kPpmd));
   };
   const size_t nc = f.coders.size();
   j.res = SZ_ERROR_UNSUPPORTED;
-  if (nc < 1 || nc > 4 || !main_ok(f.coders[0])) return j;
+  if (nc < 1 || nc > 4) return j;
+  if (!main_ok(f.coders[0], (x.flags & LZMA_GPU_7Z_PPMD) != 0 && nc <= 2)) return j;
   const uint32_t ps = x.folder_start_pack.empty() ? 0 : x.folder_start_pack[fi];
   auto pack_size = [&](uint32_t k) {
     return ps + k < a.pack_sizes.size() ? a.pack_sizes[ps + k] : uint64_t(0);
@@ -757,11 +781,88 @@ static SRes accept(const Unit& u, const LzmaGpuResult& q) {
   return SZ_OK;
 }
 
-// Decodes a list of units whose outputs go to `dst` (device) in one batch.
+// The PPMd kernel's launcher lives in ppmd7_kernels.hip; a build of this file
+// without it (the container fuzzer's host objects, tests/fuzz/) still links:
+// the reference is weak, and a PPMd folder without the kernel is an error.
+extern "C" __attribute__((weak)) int ppmd7gpu_launch(const Ppmd7GpuStreamDesc* d_descs, uint32_t n,
+                                                     const uint8_t* d_src, uint8_t* d_dst,
+                                                     uint8_t* d_ws, Ppmd7GpuResult* d_results,
+                                                     hipStream_t stream);
+
+// The PPMd units of a list as one PPMd7 batch launch on a stream of its own,
+// beside the LZMA batch: start() queues it, finish() waits and sets each
+// unit's res to SzDecodePpmd's.
+struct PpmdBatch {
+  std::vector<Unit*> which;
+  DevArr<Byte> d_ws;
+  DevArr<Ppmd7GpuStreamDesc> d_desc;
+  DevArr<Ppmd7GpuResult> d_res;
+  hipStream_t stream = nullptr;
+  ~PpmdBatch() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  SRes start(std::vector<Unit*>& us, const Byte* d_arc, Byte* dst) {
+    for (Unit* u : us)
+      if (u->method == kPpmd) which.push_back(u);
+    const size_t n = which.size();
+    if (n == 0) return SZ_OK;
+    // longest first: the launch starts its workgroups in index order
+    std::stable_sort(which.begin(), which.end(),
+                     [](const Unit* a, const Unit* b) { return a->unpack > b->unpack; });
+    std::vector<Ppmd7GpuStreamDesc> descs(n);
+    uint64_t ws = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const Unit& u = *which[k];
+      Ppmd7GpuStreamDesc& d = descs[k];
+      d.src_off = u.pack_off;
+      d.src_len = u.avail;
+      d.dst_off = u.dst_off;
+      d.dst_len = u.unpack;
+      d.order = u.props[0];
+      d.mem_size = u.props[1] | (u.props[2] << 8) | (u.props[3] << 16) | (uint32_t(u.props[4]) << 24);
+      d.ws_off = ws;
+      ws += ppmd7_slice_bytes(d.mem_size);
+    }
+    if (!d_ws.alloc(ws) || !d_desc.alloc(n) || !d_res.alloc(n)) {
+      (void)hipGetLastError();
+      set_error("7z: device allocation failed (PPMd workspace)");
+      return SZ_ERROR_MEM;
+    }
+    if (!hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "7z PPMd stream") ||
+        !hip_ok(hipMemcpy(d_desc.p, descs.data(), n * sizeof(descs[0]), hipMemcpyHostToDevice),
+                "7z H2D"))
+      return SZ_ERROR_FAIL;
+    if (!ppmd7gpu_launch ||
+        ppmd7gpu_launch(d_desc.p, uint32_t(n), d_arc, dst, d_ws.p, d_res.p, stream) != 0) {
+      set_error("7z: PPMd7 batch kernel launch failed");
+      return SZ_ERROR_FAIL;
+    }
+    return SZ_OK;
+  }
+  SRes finish() {
+    const size_t n = which.size();
+    if (n == 0) return SZ_OK;
+    std::vector<Ppmd7GpuResult> res(n);
+    if (!hip_ok(hipStreamSynchronize(stream), "7z PPMd decode") ||
+        !hip_ok(hipMemcpy(res.data(), d_res.p, n * sizeof(res[0]), hipMemcpyDeviceToHost), "7z D2H"))
+      return SZ_ERROR_FAIL;
+    for (size_t k = 0; k < n; ++k) {
+      const Unit& u = *which[k];
+      // a pack stream cut short by the archive's end cannot have been consumed whole
+      which[k]->res = res[k].res != SZ_OK ? res[k].res
+                      : u.avail != u.pack_size ? SZ_ERROR_DATA : SZ_OK;
+    }
+    return SZ_OK;
+  }
+};
+
+// Decodes a list of units whose outputs go to `dst` (device) in one batch
+// (PPMd units: PpmdBatch).
 static SRes decode_units(std::vector<Unit*>& us, const Byte* d_arc, Byte* dst) {
   std::vector<LzmaGpuStreamDesc> descs;
   std::vector<Unit*> which;
   for (Unit* u : us) {
+    if (u->method == kPpmd) continue;
     if (u->method == kCopy) {
       if (u->unpack && !hip_ok(hipMemcpyAsync(dst + u->dst_off, d_arc + u->pack_off, u->unpack,
                                               hipMemcpyDeviceToDevice, nullptr),
@@ -859,7 +960,13 @@ SRes run_jobs(std::vector<Job>& jobs, const Byte* d_arc, Byte* d_dst, uint64_t d
       units.push_back(&u);
     }
   }
-  RINOK7(decode_units(units, d_arc, d_dst));
+  {
+    PpmdBatch ppmd;
+    RINOK7(ppmd.start(units, d_arc, d_dst));
+    const SRes lz = decode_units(units, d_arc, d_dst);
+    RINOK7(ppmd.finish());  // also on an LZMA-side error: nothing stays queued
+    RINOK7(lz);
+  }
   // BCJ2 folders: the first failure in coder order, else the rc stream and
   // Bcj2_Decode (7zDec.c:423-441)
   std::vector<Bcj2GpuJob> b2;
@@ -978,6 +1085,7 @@ SRes open_archive(const Byte* arc, size_t size, Archive& x) {
     start += kStartHeader;
     if (hx.db.folders.size() != 1) return SZ_ERROR_ARCHIVE;
     hx.folder_start_pack.assign(1, 0);
+    hx.flags = x.flags;
     std::vector<Job> jobs(1, make_job(hx, hx.db, 0, start, arc, size));
     const Folder& f = hx.db.folders[0];
     if (jobs[0].res != SZ_OK) return jobs[0].res;
@@ -1011,7 +1119,8 @@ SRes open_archive(const Byte* arc, size_t size, Archive& x) {
   return read_header(x, s);
 }
 
-SRes open_checked(const Byte* arc, size_t size, Archive& x) {
+SRes open_checked(const Byte* arc, size_t size, Archive& x, unsigned flags) {
+  x.flags = flags;
   const SRes r = open_archive(arc, size, x);
   if (r != SZ_OK) x = Archive();
   return r;
@@ -1021,9 +1130,10 @@ SRes open_checked(const Byte* arc, size_t size, Archive& x) {
 
 static SRes sz_open(const Byte* archive, size_t size, LzmaGpu7zFolder* folders, size_t folder_cap,
                     size_t* n_folders, LzmaGpu7zFile* files, size_t file_cap, size_t* n_files,
-                    UInt16* names, size_t names_cap, size_t* names_len, UInt64* unpack_total) {
+                    UInt16* names, size_t names_cap, size_t* names_len, UInt64* unpack_total,
+                    unsigned flags) {
   Archive x;
-  const SRes r = open_checked(archive, size, x);
+  const SRes r = open_checked(archive, size, x, flags);
   if (n_folders) *n_folders = x.db.folders.size();
   if (n_files) *n_files = x.files.size();
   if (names_len) *names_len = x.names.size() / 2;
@@ -1089,11 +1199,11 @@ static SRes sz_open(const Byte* archive, size_t size, LzmaGpu7zFolder* folders, 
 }
 
 static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t size,
-                       SRes* file_res, size_t file_cap) {
+                       SRes* file_res, size_t file_cap, unsigned flags) {
   const SizeT cap = *destLen;
   *destLen = 0;
   Archive x;
-  SRes r = open_checked(archive, size, x);
+  SRes r = open_checked(archive, size, x, flags);
   if (r != SZ_OK) return r;
   const Ar& a = x.db;
   const size_t nf = a.folders.size(), nfiles = x.files.size();
@@ -1201,24 +1311,39 @@ static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t s
 // C ABI: no exception crosses it.  Host allocation failures (a header that
 // asks for more than the host has) return SZ_ERROR_MEM, as the reference's
 // MY_ALLOC / Buf_Create do (7zIn.c:496, 659, 1215).
-SRes LzmaGpu_7zOpen(const Byte* archive, size_t size, LzmaGpu7zFolder* folders, size_t folder_cap,
-                    size_t* n_folders, LzmaGpu7zFile* files, size_t file_cap, size_t* n_files,
-                    UInt16* names, size_t names_cap, size_t* names_len, UInt64* unpack_total) {
+SRes LzmaGpu_7zOpenEx(const Byte* archive, size_t size, LzmaGpu7zFolder* folders,
+                      size_t folder_cap, size_t* n_folders, LzmaGpu7zFile* files, size_t file_cap,
+                      size_t* n_files, UInt16* names, size_t names_cap, size_t* names_len,
+                      UInt64* unpack_total, unsigned flags) {
+  if (flags & ~LZMA_GPU_7Z_KNOWN_FLAGS) return SZ_ERROR_PARAM;
   try {
     return sz_open(archive, size, folders, folder_cap, n_folders, files, file_cap, n_files, names,
-                   names_cap, names_len, unpack_total);
+                   names_cap, names_len, unpack_total, flags);
   } catch (const std::exception&) {
     set_error("7z: host allocation failed");
     return SZ_ERROR_MEM;
   }
 }
 
-SRes LzmaGpu_7zExtract(Byte* dest, SizeT* destLen, const Byte* archive, size_t size,
-                       SRes* file_res, size_t file_cap) {
+SRes LzmaGpu_7zExtractEx(Byte* dest, SizeT* destLen, const Byte* archive, size_t size,
+                         SRes* file_res, size_t file_cap, unsigned flags) {
+  if (flags & ~LZMA_GPU_7Z_KNOWN_FLAGS) return SZ_ERROR_PARAM;
   try {
-    return sz_extract(dest, destLen, archive, size, file_res, file_cap);
+    return sz_extract(dest, destLen, archive, size, file_res, file_cap, flags);
   } catch (const std::exception&) {
     set_error("7z: host allocation failed");
     return SZ_ERROR_MEM;
   }
+}
+
+SRes LzmaGpu_7zOpen(const Byte* archive, size_t size, LzmaGpu7zFolder* folders, size_t folder_cap,
+                    size_t* n_folders, LzmaGpu7zFile* files, size_t file_cap, size_t* n_files,
+                    UInt16* names, size_t names_cap, size_t* names_len, UInt64* unpack_total) {
+  return LzmaGpu_7zOpenEx(archive, size, folders, folder_cap, n_folders, files, file_cap, n_files,
+                          names, names_cap, names_len, unpack_total, 0);
+}
+
+SRes LzmaGpu_7zExtract(Byte* dest, SizeT* destLen, const Byte* archive, size_t size,
+                       SRes* file_res, size_t file_cap) {
+  return LzmaGpu_7zExtractEx(dest, destLen, archive, size, file_res, file_cap, 0);
 }

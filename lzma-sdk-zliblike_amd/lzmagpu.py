@@ -169,6 +169,20 @@ class CSha256(ctypes.Structure):
                 ("buffer", ctypes.c_ubyte * 64)]
 
 
+class Ppmd7StreamDesc(ctypes.Structure):
+    """Ppmd7GpuStreamDesc (include/lzma_gpu.h): one PPMd7 stream of a batch."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("src_len", ctypes.c_uint64),
+                ("dst_off", ctypes.c_uint64), ("dst_len", ctypes.c_uint64),
+                ("ws_off", ctypes.c_uint64), ("mem_size", ctypes.c_uint32),
+                ("order", ctypes.c_uint32)]
+
+
+class Ppmd7Result(ctypes.Structure):
+    """Ppmd7GpuResult: SzDecodePpmd's outcome for one stream."""
+    _fields_ = [("res", ctypes.c_int32), ("_pad", ctypes.c_uint32), ("dest_len", ctypes.c_uint64),
+                ("src_len", ctypes.c_uint64)]
+
+
 class SzFolder(ctypes.Structure):
     """LzmaGpu7zFolder (include/lzma_gpu.h): one folder of an opened 7z archive."""
     _fields_ = [("pack_off", ctypes.c_uint64), ("pack_size", ctypes.c_uint64),
@@ -196,6 +210,7 @@ assert ctypes.sizeof(Session) == 192 and ctypes.sizeof(Plan) == 248
 assert ctypes.sizeof(PlanOptions) == 40
 assert ctypes.sizeof(CLzmaDec) == 136
 assert ctypes.sizeof(CSha256) == 104
+assert ctypes.sizeof(Ppmd7StreamDesc) == 48 and ctypes.sizeof(Ppmd7Result) == 24
 
 _P = ctypes.c_void_p
 _sig = {
@@ -267,6 +282,16 @@ _sig = {
                                       ctypes.c_size_t, _sp, _P, ctypes.c_size_t, _sp,
                                       ctypes.POINTER(ctypes.c_uint64)]),
     "LzmaGpu_7zExtract": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, _P, ctypes.c_size_t]),
+    "LzmaGpu_7zOpenEx": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _sp, _P,
+                                        ctypes.c_size_t, _sp, _P, ctypes.c_size_t, _sp,
+                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint]),
+    "LzmaGpu_7zExtractEx": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                           ctypes.c_uint]),
+    "Ppmd7Gpu_WorkspaceBytes": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "Ppmd7Gpu_DecodeBatch": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "Ppmd7Gpu_DecodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Ppmd7StreamDesc), ctypes.c_size_t, _P,
+                                                ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                ctypes.POINTER(Ppmd7Result), ctypes.c_uint64]),
     "LzmaGpu_DeviceCount": (ctypes.c_int, []),
     "LzmaGpu_LastError": (ctypes.c_char_p, []),
     "LzmaGpu_Version": (ctypes.c_char_p, []),
@@ -759,33 +784,73 @@ def XzDecode(data, dest_cap):
     return r, out.raw[:dl.value], bad.value
 
 
-def sz_open(data):
-    """LzmaGpu_7zOpen: (res, [SzFolder...], [SzFile...], names (UTF-16LE bytes),
-    unpack_total).  A packed header is decoded on the GPU."""
+SZ_PPMD = 1  # LZMA_GPU_7Z_PPMD: method 0x030401 folders decode (off: SZ_ERROR_UNSUPPORTED)
+
+
+def sz_open(data, flags=0):
+    """LzmaGpu_7zOpenEx: (res, [SzFolder...], [SzFile...], names (UTF-16LE bytes),
+    unpack_total).  A packed header is decoded on the GPU.  flags: SZ_PPMD."""
     nfo, nfi, nn = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
     tot = ctypes.c_uint64(0)
     src = _buf(data)
-    r = _lib.LzmaGpu_7zOpen(src, len(data), None, 0, ctypes.byref(nfo), None, 0,
-                            ctypes.byref(nfi), None, 0, ctypes.byref(nn), ctypes.byref(tot))
+    r = _lib.LzmaGpu_7zOpenEx(src, len(data), None, 0, ctypes.byref(nfo), None, 0,
+                              ctypes.byref(nfi), None, 0, ctypes.byref(nn), ctypes.byref(tot),
+                              flags)
     if r != SZ_OK:
         return r, [], [], b"", 0
     fo = (SzFolder * max(nfo.value, 1))()
     fi = (SzFile * max(nfi.value, 1))()
     names = (ctypes.c_uint16 * max(nn.value, 1))()
-    r = _lib.LzmaGpu_7zOpen(src, len(data), fo, nfo.value, ctypes.byref(nfo), fi, nfi.value,
-                            ctypes.byref(nfi), names, nn.value, ctypes.byref(nn),
-                            ctypes.byref(tot))
+    r = _lib.LzmaGpu_7zOpenEx(src, len(data), fo, nfo.value, ctypes.byref(nfo), fi, nfi.value,
+                              ctypes.byref(nfi), names, nn.value, ctypes.byref(nn),
+                              ctypes.byref(tot), flags)
     raw = bytes(bytearray(ctypes.string_at(names, 2 * nn.value)))
     return r, list(fo)[:nfo.value], list(fi)[:nfi.value], raw, tot.value
 
 
-def SzExtract(data, dest_cap, max_files=1 << 16):
-    """LzmaGpu_7zExtract: (res, extraction buffer, [per-file SRes])."""
+def SzExtract(data, dest_cap, max_files=1 << 16, flags=0):
+    """LzmaGpu_7zExtractEx: (res, extraction buffer, [per-file SRes]).  flags: SZ_PPMD."""
     out = ctypes.create_string_buffer(max(dest_cap, 1))
     dl = ctypes.c_size_t(dest_cap)
     fres = (ctypes.c_int * max_files)()
-    r = _lib.LzmaGpu_7zExtract(out, ctypes.byref(dl), _buf(data), len(data), fres, max_files)
+    r = _lib.LzmaGpu_7zExtractEx(out, ctypes.byref(dl), _buf(data), len(data), fres, max_files,
+                                 flags)
     return r, out.raw[:dl.value], list(fres)
+
+
+# ---------------------------------------------------------------- PPMd7 batches
+
+def ppmd7_workspace_bytes(mem_size):
+    """One stream's workspace slice (a multiple of 256 bytes; 0 for a bad mem_size)."""
+    return _lib.Ppmd7Gpu_WorkspaceBytes(mem_size)
+
+
+def ppmd7_make_descs(items):
+    """items: dicts with src_off, src_len, dst_off, dst_len, order, mem_size and
+    optionally ws_off.  Returns a ctypes Ppmd7StreamDesc array."""
+    arr = (Ppmd7StreamDesc * max(len(items), 1))()
+    for i, it in enumerate(items):
+        d = arr[i]
+        d.src_off, d.src_len = it["src_off"], it["src_len"]
+        d.dst_off, d.dst_len = it["dst_off"], it["dst_len"]
+        d.ws_off = it.get("ws_off", 0)
+        d.mem_size, d.order = it["mem_size"], it["order"]
+    return arr
+
+
+def ppmd7_decode_batch_device(d_descs, n, d_src, d_dst, d_ws, d_results, stream=0):
+    """Ppmd7Gpu_DecodeBatch over raw device pointers (ints)."""
+    return _lib.Ppmd7Gpu_DecodeBatch(d_descs, n, d_src, d_dst, d_ws, d_results, stream or None)
+
+
+def ppmd7_decode_batch_host(descs, n, src, dst, workspace_limit=0):
+    """Ppmd7Gpu_DecodeBatchHost: dst (bytes) is the output buffer's initial
+    contents.  Returns (res, results[ctypes], dst bytes after the call)."""
+    res = (Ppmd7Result * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.Ppmd7Gpu_DecodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
+                                      workspace_limit)
+    return r, res, d.raw[:len(dst)]
 
 
 # ---------------------------------------------------------------- streaming sessions
