@@ -27,6 +27,21 @@
  *       Lzma2Dec_DecodeToBuf    replaces Lzma2Dec.h:54-55 / Lzma2Dec.c:291-328
  *       Lzma2Decode             replaces Lzma2Dec.h:77-78 / Lzma2Dec.c:330-356
  *       LzmaDec_InitDicAndState exported like LzmaDec.c:685 (declared by Lzma2Dec.c:168)
+ *       LzmaEncProps_Init       replaces LzmaEnc.h:33 / LzmaEnc.c:45-51
+ *       LzmaEncProps_Normalize  replaces LzmaEnc.h:34 / LzmaEnc.c:53-74
+ *       LzmaEncProps_GetDictSize replaces LzmaEnc.h:35 / LzmaEnc.c:76-81
+ *       LzmaEncode              replaces LzmaEnc.h:72-74 / LzmaEnc.c:2248-2268
+ *       LzmaCompress            replaces LzmaLib.h:98-107 / LzmaLib.c:15-38
+ *
+ *     Encoding covers the reference's fast path only (algo 0 with the hash-chain
+ *     finder, what levels 0..4 select): the output is the reference's, bit for
+ *     bit.  Documented differences of LzmaEncode / LzmaCompress: props that
+ *     normalise to the optimal parser (algo 1) or a bt* finder (btMode 1) --
+ *     the default level 5 among them -- return SZ_ERROR_UNSUPPORTED with nothing
+ *     written, and LzmaGpu_LastError() says so; a source of 2^31 bytes or more
+ *     returns SZ_ERROR_UNSUPPORTED; `progress` is ignored and the allocators
+ *     are unused; LzmaEncProps_Normalize sets numThreads as a build with
+ *     threads does, and the value is unused.
  *
  *     Documented differences: no stdout print in LzmaDec_AllocateProbs (the
  *     fork's LzmaDec.c:945 debug printf); Lzma2Decode initialises its state
@@ -798,6 +813,119 @@ SRes Ppmd7Gpu_DecodeBatch(const Ppmd7GpuStreamDesc *d_descs, size_t n, const Byt
 SRes Ppmd7Gpu_DecodeBatchHost(const Ppmd7GpuStreamDesc *descs, size_t n, const Byte *src,
                               size_t src_size, Byte *dst, size_t dst_size,
                               Ppmd7GpuResult *results, uint64_t workspace_limit);
+
+/* ---------------------------------------------------------------- LZMA fast-mode encoding */
+
+/* The reference's encoder for props that normalise to algo == 0 and
+ * btMode == 0 (LzmaEncProps_Normalize, LzmaEnc.c:53-74: levels 0..4): the Hc4
+ * hash-chain finder, GetOptimumFast and the range coder, one stream per lane,
+ * many independent streams per launch (csrc/lzmaenc_device.h).  Per stream the
+ * outcome is LzmaEncode's over a buffer of dst_cap bytes:
+ *   SZ_OK                 dest_len bytes written
+ *   SZ_ERROR_OUTPUT_EOF   the stream is longer than dst_cap: dest_len == dst_cap
+ *                         and dst holds the first dst_cap bytes of the stream
+ *   SZ_ERROR_PARAM        lc > 8, lp > 4, pb > 4, dict_size 0 or above 1 << 30,
+ *                         fb outside 5..273, or ws_off not a multiple of 16;
+ *                         nothing read or written
+ *   SZ_ERROR_UNSUPPORTED  src_len >= 2^31; nothing read or written
+ * Bytes of d_dst outside [dst_off, dst_off + dest_len) are not written and
+ * bytes of d_src outside [src_off, src_off + src_len) are not read. */
+
+#ifndef __LZMA_ENC_H
+typedef struct _CLzmaEncProps {   /* 48 bytes, LzmaEnc.h:15-31 */
+  int level;
+  UInt32 dictSize;
+  int lc, lp, pb, algo, fb, btMode, numHashBytes;
+  UInt32 mc;
+  unsigned writeEndMark;
+  int numThreads;
+} CLzmaEncProps;
+#endif
+#ifndef __7Z_TYPES_H
+typedef struct {
+  SRes (*Progress)(void *p, UInt64 inSize, UInt64 outSize);
+} ICompressProgress;
+#endif
+
+void LzmaEncProps_Init(CLzmaEncProps *p);
+void LzmaEncProps_Normalize(CLzmaEncProps *p);
+UInt32 LzmaEncProps_GetDictSize(const CLzmaEncProps *props2);
+
+/* One stream of an encode batch (72 bytes).  Offsets index the caller's packed
+ * device buffers; any byte alignment for src_off / dst_off.  The props fields
+ * are the normalised ones LzmaEncGpu_DescFromProps writes. */
+typedef struct LzmaEncGpuStreamDesc {
+  uint64_t src_off;   /* plain bytes start in d_src */
+  uint64_t src_len;   /* plain bytes */
+  uint64_t dst_off;   /* output start in d_dst */
+  uint64_t dst_cap;   /* room for the output */
+  uint64_t ws_off;    /* slice start in d_workspace, bytes (LzmaEncGpu_PlanBatch) */
+  uint32_t dict_size;
+  uint32_t lc, lp, pb;
+  uint32_t fb;        /* numFastBytes, 5..273 */
+  uint32_t mc;        /* the hash chain's cut value */
+  uint32_t write_end_mark;
+  uint32_t reserved;  /* 0 */
+} LzmaEncGpuStreamDesc;
+
+/* Per-stream outcome (16 bytes). */
+typedef struct LzmaEncGpuResult {
+  int32_t res;
+  uint32_t _pad;
+  uint64_t dest_len;
+} LzmaEncGpuResult;
+
+#define LZMA_ENC_GPU_LANES_DEFAULT 0u  /* streams per wave: the library's choice */
+
+/* Host only, no device needed.  Normalises *props and applies LzmaEnc_SetProps'
+ * checks and clamps (LzmaEnc.c:391-443): SZ_ERROR_PARAM as there; then
+ * SZ_ERROR_UNSUPPORTED when the normalised props have algo != 0 or btMode != 0
+ * (LzmaGpu_LastError() says so).  On SZ_OK the props fields of *desc are set
+ * (its offsets and lengths are left alone) and props5 holds
+ * LzmaEnc_WriteProperties' 5 bytes (:2191-2218; the dictionary size is rounded
+ * up in the header only).  On an error neither is written. */
+SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps *props, int writeEndMark,
+                              LzmaEncGpuStreamDesc *desc, Byte props5[5]);
+/* Host only.  Lays the workspace out: descs[i].ws_off = start of stream i's
+ * slice (probability cells, the `matches` array, the hash, the `son` ring sized
+ * by min(dict_size, src_len) + 1; a multiple of 256 bytes; a stream the kernel
+ * rejects takes none) and *workspace_bytes = their sum.  order (n entries, may
+ * be NULL) receives the stream indices longest source first, the order the
+ * lanes should take them in.  SZ_ERROR_PARAM for n above 2^31 - 1. */
+SRes LzmaEncGpu_PlanBatch(LzmaEncGpuStreamDesc *descs, size_t n, uint32_t *order,
+                          uint64_t *workspace_bytes);
+/* Encode n streams on the current device.  All pointers are device memory
+ * owned by the caller; d_order (n indices, e.g. LzmaEncGpu_PlanBatch's) may be
+ * NULL for index order; the workspace needs no initialisation (the call clears
+ * the hashes and sets the probability cells with the whole grid before the
+ * encode kernel).  lanes: streams per 64-lane wave, 64, 32, 16 or
+ * LZMA_ENC_GPU_LANES_DEFAULT.  Asynchronous on `stream`; n == 0 is a no-op.
+ * Returns SZ_OK if the launches were queued (SZ_ERROR_FAIL without a device,
+ * SZ_ERROR_PARAM for n above 2^31 - 1 or an unknown lanes value); per-stream
+ * outcomes land in d_results[i] for stream i. */
+SRes LzmaEncGpu_EncodeBatch(const LzmaEncGpuStreamDesc *d_descs, const uint32_t *d_order, size_t n,
+                            const Byte *d_src, Byte *d_dst, void *d_workspace,
+                            LzmaEncGpuResult *d_results, unsigned lanes, void *stream);
+/* The same over host buffers: stages src and dst, plans (descs[i].ws_off is
+ * ignored), orders the streams longest first and encodes in as many launches
+ * as keep the workspace at or under workspace_limit bytes (0 = half of the
+ * device's free memory).  SZ_ERROR_MEM if one stream's slice alone exceeds the
+ * limit or an allocation fails, SZ_ERROR_PARAM for a range outside src / dst,
+ * SZ_ERROR_FAIL without a device. */
+SRes LzmaEncGpu_EncodeBatchHost(const LzmaEncGpuStreamDesc *descs, size_t n, const Byte *src,
+                                size_t src_size, Byte *dst, size_t dst_size,
+                                LzmaEncGpuResult *results, uint64_t workspace_limit);
+
+/* LzmaEnc.h:72-74 and LzmaLib.h:98-107 as one-item calls of the host form
+ * (differences: the drop-in table at the top).  A *propsSize below 5 returns
+ * SZ_ERROR_PARAM as the reference does; *destLen is written except on
+ * SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED / SZ_ERROR_FAIL. */
+SRes LzmaEncode(Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
+                const CLzmaEncProps *props, Byte *propsEncoded, SizeT *propsSize, int writeEndMark,
+                ICompressProgress *progress, ISzAlloc *alloc, ISzAlloc *allocBig);
+int LzmaCompress(unsigned char *dest, size_t *destLen, const unsigned char *src, size_t srcLen,
+                 unsigned char *outProps, size_t *outPropsSize, int level, unsigned dictSize,
+                 int lc, int lp, int pb, int fb, int numThreads);
 
 /* ---- 7z archives as folder batches ----------------
  * Replaces SzArEx_Open (7zIn.c:1314) + a SzArEx_Extract loop over every file

@@ -1,0 +1,767 @@
+// lzmaenc_device.h -- the LZMA fast-mode encoder for one stream: hash-chain
+// match finder, greedy parser and range coder, as one struct whose scalar state
+// is meant to live in registers.  A restatement of exactly what the reference's
+// LzmaEncode executes when the normalised props have algo == 0 and btMode == 0
+// (levels 0..4, LzmaEnc.c:53-74), so the output is the reference's, bit for bit:
+//
+//   match finder  Hc4_MatchFinder_GetMatches (LzFind.c:586-633),
+//                 Hc4_MatchFinder_Skip (:704-719), Hc_GetMatchesSpec (:322-351),
+//                 HASH4_CALC (LzHash.h:22-26), the geometry of MatchFinder_Create
+//                 (:191-229) and MatchFinder_Init (:271-283), in direct-input
+//                 mode (LzmaEnc.c:2057-2062, LzFind.c:61-71): the source buffer
+//                 is the window, nothing is copied or moved
+//   parser        ReadMatchDistances (LzmaEnc.c:816-849), MovePos (:803-814),
+//                 GetOptimumFast with ChangePair (:1487-1595)
+//   coder         LzmaEnc_CodeOneBlock (:1733-1893) driven as LzmaEnc_Encode2
+//                 drives it (:2154-2182), Flush / WriteEndMarker (:1597-1632),
+//                 LzmaEnc_Init (:1947-2003), the range encoder (:483-573) and
+//                 the tree / literal / length coders (:575-598, :666-691, :733-754)
+//   output        MyWrite (:2093-2105): what fits is written, the rest sets
+//                 `overflow`; the outcome is then SZ_ERROR_OUTPUT_EOF with
+//                 dest_len == dst_cap and dst holding the first dst_cap bytes of
+//                 the full stream
+//
+// Differences from the reference, all without effect on a byte of output:
+//   - no normalisation of positions (MatchFinder_Normalize): a source of 2^31
+//     bytes or more is SZ_ERROR_UNSUPPORTED, which keeps pos = dictSize + 1 +
+//     offset below kMaxValForNormalize for every dictionary up to 1 << 30;
+//   - lenLimit is min(numFastBytes, bytes left) at every position.  The
+//     reference caches it between MatchFinder_SetLimits calls (LzFind.c:246-269)
+//     but sets posLimit so that the cached value equals this one;
+//   - the ring position wraps as soon as it reaches cyclicBufferSize; the
+//     reference wraps in MatchFinder_CheckLimits (:317-318), which its posLimit
+//     reaches at the same position;
+//   - GetPosSlot is computed from the highest set bit, for every 32-bit
+//     distance (the reference's g_FastPos table covers what a 1 << 30
+//     dictionary can produce);
+//   - bytes go straight to dst; the reference collects them in a 64 KiB buffer
+//     and notices an overflow at the next buffer flush, this code at the byte
+//     that does not fit.  Both stop at the next CheckErrors (block start, block
+//     end, Flush), and bytes below dst_cap are final once written, so dst and
+//     dest_len are the same;
+//   - cacheSize is 32 bits wide (it is bounded by the output length < 2^32);
+//   - the price tables of the optimal parser are never built: the fast path
+//     reads none (LenEnc_Encode2 is called with updatePrice == !fastMode,
+//     LzmaEnc.c:1827,1836, and :1868-1874 is skipped).
+//
+// Memory of one stream (lzmaenc_layout): the probability cells, the `matches`
+// array, the hash (kFix4HashSize fixed entries + hashMask + 1) and the `son`
+// ring.  The hash must be all zero and the cells kProbInit before
+// LzmaEnc::encode runs (lzmaenc_init_slice, dealt over the whole grid on the
+// device); `matches` and `son` need no initialisation: every entry read was
+// written before, as in the reference, which does not clear `son` either.
+//
+// Bounds: every source index is below src_len (match candidates are positions
+// the finder itself inserted, so delta <= offset; the guards `delta <= off`
+// below are implied by `delta < cyclicBufferSize` and only keep a corrupted
+// hash from steering a read outside the source), every store to dst is below
+// dst_cap, and the ring index is below son_entries.
+#pragma once
+
+#include <stdint.h>
+
+#ifdef LZGPU_HOST_EMU
+#define LZENC_FN inline
+#define LZENC_HD inline
+#else
+#include <hip/hip_runtime.h>
+#define LZENC_FN __device__ __forceinline__
+#define LZENC_HD __host__ __device__ inline
+#endif
+
+namespace lzenc {
+
+constexpr int32_t kOk = 0, kErrUnsupported = 4, kErrParam = 5, kErrOutputEof = 7;
+
+constexpr uint32_t kNumStates = 12, kNumReps = 4;
+constexpr uint32_t kMatchLenMin = 2, kMatchLenMax = 273;
+constexpr uint32_t kProbInit = 1024;
+constexpr uint32_t kTopValue = 1u << 24;
+constexpr uint32_t kStartPosModelIndex = 4, kEndPosModelIndex = 14, kNumAlignBits = 4;
+constexpr uint32_t kHash2Size = 1u << 10, kHash3Size = 1u << 16;
+constexpr uint32_t kFix3HashSize = kHash2Size, kFix4HashSize = kHash2Size + kHash3Size;
+constexpr uint32_t kDictMax = 1u << 30;  // kDicLogSizeMaxCompress of a 64-bit build
+
+// probability cells (16-bit), fixed sections first, literals last
+constexpr uint32_t kIsMatch = 0;                         // [12][16]
+constexpr uint32_t kIsRep = kIsMatch + kNumStates * 16;  // [12]
+constexpr uint32_t kIsRepG0 = kIsRep + kNumStates;
+constexpr uint32_t kIsRepG1 = kIsRepG0 + kNumStates;
+constexpr uint32_t kIsRepG2 = kIsRepG1 + kNumStates;
+constexpr uint32_t kIsRep0Long = kIsRepG2 + kNumStates;      // [12][16]
+constexpr uint32_t kPosSlot = kIsRep0Long + kNumStates * 16;  // [4][64]
+constexpr uint32_t kPosEncoders = kPosSlot + 4 * 64;          // [128 - 14]
+constexpr uint32_t kPosAlign = kPosEncoders + 128 - kEndPosModelIndex;  // [16]
+constexpr uint32_t kLenEnc = kPosAlign + 16;   // choice, choice2, low[128], mid[128], high[256]
+constexpr uint32_t kLenCells = 2 + 128 + 128 + 256;
+constexpr uint32_t kRepLenEnc = kLenEnc + kLenCells;
+constexpr uint32_t kLit = kRepLenEnc + kLenCells;
+constexpr uint32_t kLenLow = 2, kLenMid = 2 + 128, kLenHigh = 2 + 256;
+
+// room for the reference's matches[LZMA_MATCH_LEN_MAX * 2 + 2 + 1]
+constexpr uint32_t kMatchesWords = 552;
+
+struct Params {
+  uint32_t dict_size, lc, lp, pb, fb, mc, write_end_mark;
+};
+
+// SZ_OK, or what the stream ends with before anything is read or written
+LZENC_HD int32_t check_params(const Params& q, uint64_t src_len) {
+  if (q.lc > 8 || q.lp > 4 || q.pb > 4 || q.dict_size == 0 || q.dict_size > kDictMax ||
+      q.fb < 5 || q.fb > kMatchLenMax)
+    return kErrParam;
+  if (src_len >= (uint64_t(1) << 31)) return kErrUnsupported;
+  return kOk;
+}
+
+// MatchFinder_Create's hashMask for numHashBytes == 4 (LzFind.c:200-215)
+LZENC_HD uint32_t hash_mask(uint32_t dict_size) {
+  uint32_t hs = dict_size - 1;
+  hs |= hs >> 1;
+  hs |= hs >> 2;
+  hs |= hs >> 4;
+  hs |= hs >> 8;
+  hs >>= 1;
+  hs |= 0xFFFF;
+  if (hs > (1u << 24)) hs >>= 1;
+  return hs;
+}
+
+// One stream's slice of the workspace, offsets in bytes from the slice start
+// (each a multiple of 16), `bytes` a multiple of 256.
+struct Layout {
+  uint64_t probs, matches, hash, son, bytes;
+  uint32_t prob_cells, hash_words, son_entries;
+};
+LZENC_HD Layout lzmaenc_layout(const Params& q, uint64_t src_len) {
+  Layout l;
+  l.prob_cells = kLit + (0x300u << (q.lc + q.lp));
+  l.hash_words = kFix4HashSize + hash_mask(q.dict_size) + 1;
+  // a stream no longer than its dictionary never wraps the ring
+  l.son_entries = uint32_t(src_len < q.dict_size ? src_len : q.dict_size) + 1;
+  l.probs = 0;
+  l.matches = (uint64_t(l.prob_cells) * 2 + 15) & ~uint64_t(15);
+  l.hash = l.matches + kMatchesWords * 4;
+  l.son = l.hash + uint64_t(l.hash_words) * 4;
+  l.bytes = (l.son + uint64_t(l.son_entries) * 4 + 255) & ~uint64_t(255);
+  return l;
+}
+
+// ---------------------------------------------------------------- props (host side)
+// CLzmaEncProps (LzmaEnc.h:15-31), field for field
+struct EncProps {
+  int level;
+  uint32_t dictSize;
+  int lc, lp, pb, algo, fb, btMode, numHashBytes;
+  uint32_t mc;
+  unsigned writeEndMark;
+  int numThreads;
+};
+// LzmaEncProps_Init (LzmaEnc.c:45-51)
+LZENC_HD void props_init(EncProps* p) {
+  p->level = 5;
+  p->dictSize = p->mc = 0;
+  p->lc = p->lp = p->pb = p->algo = p->fb = p->btMode = p->numHashBytes = p->numThreads = -1;
+  p->writeEndMark = 0;
+}
+// LzmaEncProps_Normalize (LzmaEnc.c:53-74) of a build with threads (no _7ZIP_ST)
+LZENC_HD void props_normalize(EncProps* p) {
+  int level = p->level;
+  if (level < 0) level = 5;
+  p->level = level;
+  if (p->dictSize == 0)
+    p->dictSize = (level <= 5 ? (1u << (level * 2 + 14)) : (level == 6 ? (1u << 25) : (1u << 26)));
+  if (p->lc < 0) p->lc = 3;
+  if (p->lp < 0) p->lp = 0;
+  if (p->pb < 0) p->pb = 2;
+  if (p->algo < 0) p->algo = (level < 5 ? 0 : 1);
+  if (p->fb < 0) p->fb = (level < 7 ? 32 : 64);
+  if (p->btMode < 0) p->btMode = (p->algo == 0 ? 0 : 1);
+  if (p->numHashBytes < 0) p->numHashBytes = 4;
+  if (p->mc == 0) p->mc = (16 + (uint32_t(p->fb) >> 1)) >> (p->btMode ? 0 : 1);
+  if (p->numThreads < 0) p->numThreads = ((p->btMode && p->algo) ? 2 : 1);
+}
+// LzmaEnc_SetProps' checks and clamps (LzmaEnc.c:391-443) into the encoder's
+// parameters: SZ_ERROR_PARAM as there, then SZ_ERROR_UNSUPPORTED for what is
+// not the fast path (algo != 0 or btMode != 0).  q is written only on SZ_OK.
+LZENC_HD int32_t params_from_props(const EncProps* props2, int writeEndMark, Params* q) {
+  EncProps props = *props2;
+  props_normalize(&props);
+  if (props.lc > 8 || props.lp > 4 || props.pb > 4 || props.dictSize > kDictMax) return kErrParam;
+  if (props.algo != 0 || props.btMode != 0) return kErrUnsupported;
+  uint32_t fb = uint32_t(props.fb);
+  if (fb < 5) fb = 5;
+  if (fb > kMatchLenMax) fb = kMatchLenMax;
+  q->dict_size = props.dictSize;
+  q->lc = uint32_t(props.lc);
+  q->lp = uint32_t(props.lp);
+  q->pb = uint32_t(props.pb);
+  q->fb = fb;
+  q->mc = props.mc;
+  q->write_end_mark = writeEndMark ? 1u : 0u;
+  return kOk;
+}
+// LzmaEnc_WriteProperties (LzmaEnc.c:2191-2218): the dictionary size is
+// rounded up to 2^n or 3 * 2^(n-1) in the header only
+LZENC_HD void write_props5(const Params& q, uint8_t* props5) {
+  uint32_t dictSize = q.dict_size;
+  props5[0] = uint8_t((q.pb * 5 + q.lp) * 9 + q.lc);
+  for (int i = 11; i <= 30; i++) {
+    if (dictSize <= (2u << i)) {
+      dictSize = (2u << i);
+      break;
+    }
+    if (dictSize <= (3u << i)) {
+      dictSize = (3u << i);
+      break;
+    }
+  }
+  for (int i = 0; i < 4; i++) props5[1 + i] = uint8_t(dictSize >> (8 * i));
+}
+
+// p->crc[] of the match finder (LzFind.c:141-148): the project's CRC-32 table
+// (slice 0 of crc32_device.h's CrcTables, polynomial kCrcPoly), entry v
+LZENC_HD uint32_t crc_entry(uint32_t v) {
+  uint32_t r = v;
+  for (int j = 0; j < 8; ++j) r = (r >> 1) ^ ((r & 1u) ? 0xEDB88320u : 0u);
+  return r;
+}
+
+struct Out {
+  int32_t res;
+  uint64_t dest_len;
+};
+
+struct LzmaEnc {
+  // memory
+  const uint8_t* src;
+  uint8_t* dst;
+  uint16_t* probs;
+  uint32_t* matches;
+  uint32_t* hash;
+  uint32_t* son;
+  const uint32_t* crc;
+  // props
+  uint32_t src_len, lc, lpMask, pbMask, numFastBytes, cutValue, writeEndMark;
+  uint32_t hashMask, cyclicBufferSize;
+  uint64_t dst_cap;
+  // match finder: off = buffer - bufferBase; pos = cyclicBufferSize + off
+  uint32_t off, cyclicBufferPos;
+  // parser
+  uint32_t longestMatchLength, numPairs, numAvail, additionalOffset;
+  uint32_t rep0, rep1, rep2, rep3, state;
+  // range coder
+  uint64_t low, outPos;
+  uint32_t range, cacheSize, cache;
+  // driver
+  uint32_t nowPos64, finished, overflow;
+
+  // ---------------------------------------------------------------- range coder
+  LZENC_FN void put_byte(uint32_t b) {
+    if (outPos < dst_cap)
+      dst[outPos] = uint8_t(b);
+    else
+      overflow = 1;
+    ++outPos;
+  }
+  LZENC_FN void shift_low() {
+    if (uint32_t(low) < 0xFF000000u || uint32_t(low >> 32) != 0) {
+      uint32_t temp = cache;
+      do {
+        put_byte(temp + uint32_t(low >> 32));
+        temp = 0xFF;
+      } while (--cacheSize != 0);
+      cache = uint32_t(low) >> 24;
+    }
+    cacheSize++;
+    low = uint32_t(uint32_t(low) << 8);
+  }
+  LZENC_FN void flush_data() {
+    for (int i = 0; i < 5; i++) shift_low();
+  }
+  LZENC_FN void encode_direct_bits(uint32_t value, int numBits) {
+    do {
+      range >>= 1;
+      low += range & (0u - ((value >> --numBits) & 1));
+      if (range < kTopValue) {
+        range <<= 8;
+        shift_low();
+      }
+    } while (numBits != 0);
+  }
+  LZENC_FN void encode_bit(uint32_t cell, uint32_t symbol) {
+    uint32_t ttt = probs[cell];
+    const uint32_t newBound = (range >> 11) * ttt;
+    if (symbol == 0) {
+      range = newBound;
+      ttt += (2048 - ttt) >> 5;
+    } else {
+      low += newBound;
+      range -= newBound;
+      ttt -= ttt >> 5;
+    }
+    probs[cell] = uint16_t(ttt);
+    if (range < kTopValue) {
+      range <<= 8;
+      shift_low();
+    }
+  }
+  LZENC_FN void lit_encode(uint32_t base, uint32_t symbol) {
+    symbol |= 0x100;
+    do {
+      encode_bit(base + (symbol >> 8), (symbol >> 7) & 1);
+      symbol <<= 1;
+    } while (symbol < 0x10000);
+  }
+  LZENC_FN void lit_encode_matched(uint32_t base, uint32_t symbol, uint32_t matchByte) {
+    uint32_t offs = 0x100;
+    symbol |= 0x100;
+    do {
+      matchByte <<= 1;
+      encode_bit(base + offs + (matchByte & offs) + (symbol >> 8), (symbol >> 7) & 1);
+      symbol <<= 1;
+      offs &= ~(matchByte ^ symbol);
+    } while (symbol < 0x10000);
+  }
+  LZENC_FN void tree_encode(uint32_t base, int numBitLevels, uint32_t symbol) {
+    uint32_t m = 1;
+    for (int i = numBitLevels; i != 0;) {
+      i--;
+      const uint32_t bit = (symbol >> i) & 1;
+      encode_bit(base + m, bit);
+      m = (m << 1) | bit;
+    }
+  }
+  LZENC_FN void tree_reverse_encode(uint32_t base, int numBitLevels, uint32_t symbol) {
+    uint32_t m = 1;
+    for (int i = 0; i < numBitLevels; i++) {
+      const uint32_t bit = symbol & 1;
+      encode_bit(base + m, bit);
+      m = (m << 1) | bit;
+      symbol >>= 1;
+    }
+  }
+  LZENC_FN void len_encode(uint32_t base, uint32_t symbol, uint32_t posState) {
+    if (symbol < 8) {
+      encode_bit(base, 0);
+      tree_encode(base + kLenLow + (posState << 3), 3, symbol);
+    } else {
+      encode_bit(base, 1);
+      if (symbol < 16) {
+        encode_bit(base + 1, 0);
+        tree_encode(base + kLenMid + (posState << 3), 3, symbol - 8);
+      } else {
+        encode_bit(base + 1, 1);
+        tree_encode(base + kLenHigh, 8, symbol - 16);
+      }
+    }
+  }
+
+  // ---------------------------------------------------------------- match finder
+  LZENC_FN uint32_t avail() const { return src_len - off; }
+  LZENC_FN void move_pos() {
+    if (++cyclicBufferPos == cyclicBufferSize) cyclicBufferPos = 0;
+    ++off;
+  }
+  // HASH4_CALC and the three table updates; returns the head of the 4-byte chain
+  LZENC_FN uint32_t hash_insert(const uint8_t* cur, uint32_t pos, uint32_t* d2, uint32_t* d3) {
+    const uint32_t temp = crc[cur[0]] ^ cur[1];
+    const uint32_t hash2Value = temp & (kHash2Size - 1);
+    const uint32_t hash3Value = (temp ^ (uint32_t(cur[2]) << 8)) & (kHash3Size - 1);
+    const uint32_t hashValue = (temp ^ (uint32_t(cur[2]) << 8) ^ (crc[cur[3]] << 5)) & hashMask;
+    *d2 = pos - hash[hash2Value];
+    *d3 = pos - hash[kFix3HashSize + hash3Value];
+    const uint32_t curMatch = hash[kFix4HashSize + hashValue];
+    hash[hash2Value] = pos;
+    hash[kFix3HashSize + hash3Value] = pos;
+    hash[kFix4HashSize + hashValue] = pos;
+    return curMatch;
+  }
+  LZENC_FN uint32_t hc_get_matches_spec(uint32_t lenLimit, uint32_t curMatch, uint32_t pos,
+                                        const uint8_t* cur, uint32_t cutValue_, uint32_t offset,
+                                        uint32_t maxLen) {
+    son[cyclicBufferPos] = curMatch;
+    for (;;) {
+      const uint32_t delta = pos - curMatch;
+      if (cutValue_-- == 0 || delta >= cyclicBufferSize || delta > off) return offset;
+      const uint8_t* pb = cur - delta;
+      curMatch = son[cyclicBufferPos - delta + ((delta > cyclicBufferPos) ? cyclicBufferSize : 0)];
+      if (pb[maxLen] == cur[maxLen] && *pb == *cur) {
+        uint32_t len = 0;
+        while (++len != lenLimit)
+          if (pb[len] != cur[len]) break;
+        if (maxLen < len) {
+          matches[offset++] = maxLen = len;
+          matches[offset++] = delta - 1;
+          if (len == lenLimit) return offset;
+        }
+      }
+    }
+  }
+  // Hc4_MatchFinder_GetMatches into `matches`; returns 2 * pairs
+  LZENC_FN uint32_t get_matches() {
+    uint32_t lenLimit = avail();
+    if (lenLimit > numFastBytes) lenLimit = numFastBytes;
+    if (lenLimit < 4) {
+      move_pos();
+      return 0;
+    }
+    const uint8_t* cur = src + off;
+    const uint32_t pos = cyclicBufferSize + off;
+    uint32_t delta2, delta3;
+    const uint32_t curMatch = hash_insert(cur, pos, &delta2, &delta3);
+    uint32_t maxLen = 1, offset = 0;
+    if (delta2 < cyclicBufferSize && delta2 <= off && *(cur - delta2) == *cur) {
+      matches[0] = maxLen = 2;
+      matches[1] = delta2 - 1;
+      offset = 2;
+    }
+    if (delta2 != delta3 && delta3 < cyclicBufferSize && delta3 <= off && *(cur - delta3) == *cur) {
+      maxLen = 3;
+      matches[offset + 1] = delta3 - 1;
+      offset += 2;
+      delta2 = delta3;
+    }
+    if (offset != 0) {
+      for (; maxLen != lenLimit; maxLen++)
+        if (*(cur + maxLen - delta2) != cur[maxLen]) break;
+      matches[offset - 2] = maxLen;
+      if (maxLen == lenLimit) {
+        son[cyclicBufferPos] = curMatch;
+        move_pos();
+        return offset;
+      }
+    }
+    if (maxLen < 3) maxLen = 3;
+    offset = hc_get_matches_spec(lenLimit, curMatch, pos, cur, cutValue, offset, maxLen);
+    move_pos();
+    return offset;
+  }
+  // Hc4_MatchFinder_Skip
+  LZENC_FN void skip(uint32_t num) {
+    do {
+      if (avail() < 4) {  // lenLimit < 4 (numFastBytes >= 5)
+        move_pos();
+        continue;
+      }
+      uint32_t delta2, delta3;
+      const uint32_t curMatch = hash_insert(src + off, cyclicBufferSize + off, &delta2, &delta3);
+      son[cyclicBufferPos] = curMatch;
+      move_pos();
+    } while (--num != 0);
+  }
+
+  // ---------------------------------------------------------------- parser
+  LZENC_FN void parser_move_pos(uint32_t num) {
+    if (num != 0) {
+      additionalOffset += num;
+      skip(num);
+    }
+  }
+  LZENC_FN uint32_t read_match_distances(uint32_t* numDistancePairsRes) {
+    uint32_t lenRes = 0;
+    numAvail = avail();
+    const uint32_t pairs = get_matches();
+    if (pairs > 0) {
+      lenRes = matches[pairs - 2];
+      if (lenRes == numFastBytes) {
+        const uint8_t* pby = src + off - 1;
+        const uint32_t distance = matches[pairs - 1] + 1;
+        uint32_t na = numAvail;
+        if (na > kMatchLenMax) na = kMatchLenMax;
+        const uint8_t* pby2 = pby - distance;
+        for (; lenRes < na && pby[lenRes] == pby2[lenRes]; lenRes++) {
+        }
+      }
+    }
+    additionalOffset++;
+    *numDistancePairsRes = pairs;
+    return lenRes;
+  }
+  LZENC_FN uint32_t rep(uint32_t i) const {
+    return i == 0 ? rep0 : i == 1 ? rep1 : i == 2 ? rep2 : rep3;
+  }
+  static LZENC_FN bool change_pair(uint32_t smallDist, uint32_t bigDist) {
+    return (bigDist >> 7) > smallDist;
+  }
+  LZENC_FN uint32_t get_optimum_fast(uint32_t* backRes) {
+    uint32_t mainLen, mainDist, pairs, repIndex, repLen;
+    if (additionalOffset == 0)
+      mainLen = read_match_distances(&pairs);
+    else {
+      mainLen = longestMatchLength;
+      pairs = numPairs;
+    }
+    uint32_t na = numAvail;
+    *backRes = 0xFFFFFFFFu;
+    if (na < 2) return 1;
+    if (na > kMatchLenMax) na = kMatchLenMax;
+    const uint8_t* data = src + off - 1;
+
+    repLen = repIndex = 0;
+    for (uint32_t i = 0; i < kNumReps; i++) {
+      const uint8_t* data2 = data - (rep(i) + 1);
+      if (data[0] != data2[0] || data[1] != data2[1]) continue;
+      uint32_t len;
+      for (len = 2; len < na && data[len] == data2[len]; len++) {
+      }
+      if (len >= numFastBytes) {
+        *backRes = i;
+        parser_move_pos(len - 1);
+        return len;
+      }
+      if (len > repLen) {
+        repIndex = i;
+        repLen = len;
+      }
+    }
+
+    if (mainLen >= numFastBytes) {
+      *backRes = matches[pairs - 1] + kNumReps;
+      parser_move_pos(mainLen - 1);
+      return mainLen;
+    }
+
+    mainDist = 0;
+    if (mainLen >= 2) {
+      mainDist = matches[pairs - 1];
+      while (pairs > 2 && mainLen == matches[pairs - 4] + 1) {
+        if (!change_pair(matches[pairs - 3], mainDist)) break;
+        pairs -= 2;
+        mainLen = matches[pairs - 2];
+        mainDist = matches[pairs - 1];
+      }
+      if (mainLen == 2 && mainDist >= 0x80) mainLen = 1;
+    }
+
+    if (repLen >= 2 && ((repLen + 1 >= mainLen) || (repLen + 2 >= mainLen && mainDist >= (1u << 9)) ||
+                        (repLen + 3 >= mainLen && mainDist >= (1u << 15)))) {
+      *backRes = repIndex;
+      parser_move_pos(repLen - 1);
+      return repLen;
+    }
+
+    if (mainLen < 2 || na <= 2) return 1;
+
+    longestMatchLength = read_match_distances(&numPairs);
+    if (longestMatchLength >= 2) {
+      const uint32_t newDistance = matches[numPairs - 1];
+      if ((longestMatchLength >= mainLen && newDistance < mainDist) ||
+          (longestMatchLength == mainLen + 1 && !change_pair(mainDist, newDistance)) ||
+          (longestMatchLength > mainLen + 1) ||
+          (longestMatchLength + 1 >= mainLen && mainLen >= 3 && change_pair(newDistance, mainDist)))
+        return 1;
+    }
+
+    data = src + off - 1;
+    for (uint32_t i = 0; i < kNumReps; i++) {
+      const uint8_t* data2 = data - (rep(i) + 1);
+      if (data[0] != data2[0] || data[1] != data2[1]) continue;
+      const uint32_t limit = mainLen - 1;
+      uint32_t len;
+      for (len = 2; len < limit && data[len] == data2[len]; len++) {
+      }
+      if (len >= limit) return 1;
+    }
+    *backRes = mainDist + kNumReps;
+    parser_move_pos(mainLen - 2);
+    return mainLen;
+  }
+
+  // ---------------------------------------------------------------- coder
+  // kLiteralNextStates, kMatchNextStates, kRepNextStates, kShortRepNextStates
+  static LZENC_FN uint32_t lit_next(uint32_t s) { return s < 4 ? 0 : s < 10 ? s - 3 : s - 6; }
+  static LZENC_FN uint32_t match_next(uint32_t s) { return s < 7 ? 7 : 10; }
+  static LZENC_FN uint32_t rep_next(uint32_t s) { return s < 7 ? 8 : 11; }
+  static LZENC_FN uint32_t short_rep_next(uint32_t s) { return s < 7 ? 9 : 11; }
+  static LZENC_FN uint32_t len_to_pos_state(uint32_t len) { return len < 5 ? len - 2 : 3; }
+  static LZENC_FN uint32_t get_pos_slot(uint32_t pos) {
+    if (pos < 2) return pos;
+    const uint32_t i = 31 - uint32_t(__builtin_clz(pos));
+    return (i + i) + ((pos >> (i - 1)) & 1);
+  }
+
+  LZENC_FN void write_end_marker(uint32_t posState) {
+    encode_bit(kIsMatch + state * 16 + posState, 1);
+    encode_bit(kIsRep + state, 0);
+    state = match_next(state);
+    const uint32_t len = kMatchLenMin;
+    len_encode(kLenEnc, len - kMatchLenMin, posState);
+    tree_encode(kPosSlot + len_to_pos_state(len) * 64, 6, (1 << 6) - 1);
+    encode_direct_bits(((1u << 30) - 1) >> kNumAlignBits, 30 - kNumAlignBits);
+    tree_reverse_encode(kPosAlign, kNumAlignBits, (1 << kNumAlignBits) - 1);
+  }
+  // CheckErrors: true when the stream has failed (the only failure is a write
+  // that did not fit, the reference's rc.res / SZ_ERROR_WRITE)
+  LZENC_FN bool check_errors() {
+    if (overflow) finished = 1;
+    return overflow != 0;
+  }
+  LZENC_FN void flush(uint32_t nowPos) {
+    finished = 1;
+    if (writeEndMark) write_end_marker(nowPos & pbMask);
+    flush_data();
+  }
+
+  LZENC_FN void code_one_block() {
+    if (check_errors()) return;
+    uint32_t nowPos32 = nowPos64;
+    const uint32_t startPos32 = nowPos32;
+
+    if (nowPos64 == 0) {
+      uint32_t pairs;
+      if (avail() == 0) {
+        flush(nowPos32);
+        return;
+      }
+      read_match_distances(&pairs);
+      encode_bit(kIsMatch + state * 16, 0);
+      state = lit_next(state);
+      const uint32_t curByte = src[off - additionalOffset];
+      lit_encode(kLit, curByte);
+      additionalOffset--;
+      nowPos32++;
+    }
+
+    if (avail() != 0)
+      for (;;) {
+        uint32_t pos;
+        const uint32_t len = get_optimum_fast(&pos);
+        const uint32_t posState = nowPos32 & pbMask;
+        if (len == 1 && pos == 0xFFFFFFFFu) {
+          encode_bit(kIsMatch + state * 16 + posState, 0);
+          const uint8_t* data = src + off - additionalOffset;
+          const uint32_t curByte = *data;
+          const uint32_t lit =
+              kLit + (((nowPos32 & lpMask) << lc) + (uint32_t(*(data - 1)) >> (8 - lc))) * 0x300;
+          if (state < 7)
+            lit_encode(lit, curByte);
+          else
+            lit_encode_matched(lit, curByte, *(data - rep0 - 1));
+          state = lit_next(state);
+        } else {
+          encode_bit(kIsMatch + state * 16 + posState, 1);
+          if (pos < kNumReps) {
+            encode_bit(kIsRep + state, 1);
+            if (pos == 0) {
+              encode_bit(kIsRepG0 + state, 0);
+              encode_bit(kIsRep0Long + state * 16 + posState, (len == 1) ? 0 : 1);
+            } else {
+              const uint32_t distance = rep(pos);
+              encode_bit(kIsRepG0 + state, 1);
+              if (pos == 1)
+                encode_bit(kIsRepG1 + state, 0);
+              else {
+                encode_bit(kIsRepG1 + state, 1);
+                encode_bit(kIsRepG2 + state, pos - 2);
+                if (pos == 3) rep3 = rep2;
+                rep2 = rep1;
+              }
+              rep1 = rep0;
+              rep0 = distance;
+            }
+            if (len == 1)
+              state = short_rep_next(state);
+            else {
+              len_encode(kRepLenEnc, len - kMatchLenMin, posState);
+              state = rep_next(state);
+            }
+          } else {
+            encode_bit(kIsRep + state, 0);
+            state = match_next(state);
+            len_encode(kLenEnc, len - kMatchLenMin, posState);
+            pos -= kNumReps;
+            const uint32_t posSlot = get_pos_slot(pos);
+            tree_encode(kPosSlot + len_to_pos_state(len) * 64, 6, posSlot);
+            if (posSlot >= kStartPosModelIndex) {
+              const uint32_t footerBits = (posSlot >> 1) - 1;
+              const uint32_t base = (2 | (posSlot & 1)) << footerBits;
+              const uint32_t posReduced = pos - base;
+              if (posSlot < kEndPosModelIndex)
+                tree_reverse_encode(kPosEncoders + base - posSlot - 1, int(footerBits), posReduced);
+              else {
+                encode_direct_bits(posReduced >> kNumAlignBits, int(footerBits - kNumAlignBits));
+                tree_reverse_encode(kPosAlign, kNumAlignBits, posReduced & 15);
+              }
+            }
+            rep3 = rep2;
+            rep2 = rep1;
+            rep1 = rep0;
+            rep0 = pos;
+          }
+        }
+        additionalOffset -= len;
+        nowPos32 += len;
+        if (additionalOffset == 0) {
+          if (avail() == 0) break;
+          const uint32_t processed = nowPos32 - startPos32;
+          if (processed >= (1u << 15)) {
+            nowPos64 += nowPos32 - startPos32;
+            check_errors();
+            return;
+          }
+        }
+      }
+    nowPos64 += nowPos32 - startPos32;
+    flush(nowPos32);
+  }
+
+  // LzmaEnc_MemEncode after LzmaEnc_SetProps: q has passed check_params
+  LZENC_FN Out encode(const uint8_t* src_, uint32_t src_len_, uint8_t* dst_, uint64_t dst_cap_,
+                      const Params& q, uint8_t* slice, const Layout& l, const uint32_t* crc_) {
+    src = src_;
+    dst = dst_;
+    probs = reinterpret_cast<uint16_t*>(slice + l.probs);
+    matches = reinterpret_cast<uint32_t*>(slice + l.matches);
+    hash = reinterpret_cast<uint32_t*>(slice + l.hash);
+    son = reinterpret_cast<uint32_t*>(slice + l.son);
+    crc = crc_;
+    src_len = src_len_;
+    dst_cap = dst_cap_;
+    lc = q.lc;
+    lpMask = (1u << q.lp) - 1;
+    pbMask = (1u << q.pb) - 1;
+    numFastBytes = q.fb;
+    cutValue = q.mc;
+    writeEndMark = q.write_end_mark;
+    hashMask = hash_mask(q.dict_size);
+    cyclicBufferSize = q.dict_size + 1;
+    // MatchFinder_Init
+    off = 0;
+    cyclicBufferPos = 0;
+    // LzmaEnc_Init
+    state = 0;
+    rep0 = rep1 = rep2 = rep3 = 0;
+    low = 0;
+    range = 0xFFFFFFFFu;
+    cacheSize = 1;
+    cache = 0;
+    outPos = 0;
+    additionalOffset = 0;
+    longestMatchLength = numPairs = numAvail = 0;
+    nowPos64 = 0;
+    finished = 0;
+    overflow = 0;
+    // LzmaEnc_Encode2
+    for (;;) {
+      code_one_block();
+      if (finished) break;
+    }
+    Out o;
+    o.res = overflow ? kErrOutputEof : kOk;
+    o.dest_len = overflow ? dst_cap : outPos;
+    return o;
+  }
+};
+
+// Cells [first, first + step, ...) of a slice's probability tables to
+// kProbInit and its hash words to 0: lane `first` of `step` (the host build is
+// lane 0 of 1; on the device the whole grid shares the work).
+LZENC_FN void lzmaenc_init_slice(uint8_t* slice, const Layout& l, uint64_t first, uint64_t step) {
+  uint16_t* probs = reinterpret_cast<uint16_t*>(slice + l.probs);
+  for (uint64_t i = first; i < l.prob_cells; i += step) probs[i] = uint16_t(kProbInit);
+  uint32_t* hash = reinterpret_cast<uint32_t*>(slice + l.hash);
+  for (uint64_t i = first; i < l.hash_words; i += step) hash[i] = 0;
+}
+
+}  // namespace lzenc

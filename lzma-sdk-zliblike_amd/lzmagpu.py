@@ -7,8 +7,10 @@ bench.py.  Function names and argument meaning follow the reference C API
 out-parameters, plus the output bytes.
 
 There is no fallback: if lib/liblzmagpu.so is missing this module raises at
-import time, and on a machine without a HIP device every decode returns
-SZ_ERROR_FAIL (``LzmaGpu_LastError`` says why).
+import time, and on a machine without a HIP device every decode and encode
+returns SZ_ERROR_FAIL (``LzmaGpu_LastError`` says why).  Encoding (the
+reference's fast path, levels 0..4): ``encode_batch``, ``LzmaEncode``,
+``LzmaCompress`` and the ``LzmaEncGpu_*`` batch calls.
 """
 import ctypes
 import os
@@ -183,6 +185,30 @@ class Ppmd7Result(ctypes.Structure):
                 ("src_len", ctypes.c_uint64)]
 
 
+class CLzmaEncProps(ctypes.Structure):
+    """CLzmaEncProps (LzmaEnc.h:15-31)."""
+    _fields_ = [("level", ctypes.c_int), ("dictSize", ctypes.c_uint32), ("lc", ctypes.c_int),
+                ("lp", ctypes.c_int), ("pb", ctypes.c_int), ("algo", ctypes.c_int),
+                ("fb", ctypes.c_int), ("btMode", ctypes.c_int), ("numHashBytes", ctypes.c_int),
+                ("mc", ctypes.c_uint32), ("writeEndMark", ctypes.c_uint),
+                ("numThreads", ctypes.c_int)]
+
+
+class EncStreamDesc(ctypes.Structure):
+    """LzmaEncGpuStreamDesc (include/lzma_gpu.h): one stream of an encode batch."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("src_len", ctypes.c_uint64),
+                ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64),
+                ("ws_off", ctypes.c_uint64), ("dict_size", ctypes.c_uint32),
+                ("lc", ctypes.c_uint32), ("lp", ctypes.c_uint32), ("pb", ctypes.c_uint32),
+                ("fb", ctypes.c_uint32), ("mc", ctypes.c_uint32),
+                ("write_end_mark", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class EncResult(ctypes.Structure):
+    """LzmaEncGpuResult: LzmaEncode's outcome for one stream."""
+    _fields_ = [("res", ctypes.c_int32), ("_pad", ctypes.c_uint32), ("dest_len", ctypes.c_uint64)]
+
+
 class SzFolder(ctypes.Structure):
     """LzmaGpu7zFolder (include/lzma_gpu.h): one folder of an opened 7z archive."""
     _fields_ = [("pack_off", ctypes.c_uint64), ("pack_size", ctypes.c_uint64),
@@ -211,6 +237,8 @@ assert ctypes.sizeof(PlanOptions) == 40
 assert ctypes.sizeof(CLzmaDec) == 136
 assert ctypes.sizeof(CSha256) == 104
 assert ctypes.sizeof(Ppmd7StreamDesc) == 48 and ctypes.sizeof(Ppmd7Result) == 24
+assert ctypes.sizeof(CLzmaEncProps) == 48
+assert ctypes.sizeof(EncStreamDesc) == 72 and ctypes.sizeof(EncResult) == 16
 
 _P = ctypes.c_void_p
 _sig = {
@@ -292,6 +320,23 @@ _sig = {
     "Ppmd7Gpu_DecodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Ppmd7StreamDesc), ctypes.c_size_t, _P,
                                                 ctypes.c_size_t, _P, ctypes.c_size_t,
                                                 ctypes.POINTER(Ppmd7Result), ctypes.c_uint64]),
+    "LzmaEncProps_Init": (None, [ctypes.POINTER(CLzmaEncProps)]),
+    "LzmaEncProps_Normalize": (None, [ctypes.POINTER(CLzmaEncProps)]),
+    "LzmaEncProps_GetDictSize": (ctypes.c_uint32, [ctypes.POINTER(CLzmaEncProps)]),
+    "LzmaEncGpu_DescFromProps": (ctypes.c_int, [ctypes.POINTER(CLzmaEncProps), ctypes.c_int,
+                                                ctypes.POINTER(EncStreamDesc), ctypes.c_char_p]),
+    "LzmaEncGpu_PlanBatch": (ctypes.c_int, [ctypes.POINTER(EncStreamDesc), ctypes.c_size_t, _P,
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+    "LzmaEncGpu_EncodeBatch": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P,
+                                              ctypes.c_uint, _P]),
+    "LzmaEncGpu_EncodeBatchHost": (ctypes.c_int, [ctypes.POINTER(EncStreamDesc), ctypes.c_size_t,
+                                                  _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                  ctypes.POINTER(EncResult), ctypes.c_uint64]),
+    "LzmaEncode": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, ctypes.POINTER(CLzmaEncProps), _P,
+                                  _sp, ctypes.c_int, _P, _P, _P]),
+    "LzmaCompress": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, _P, _sp, ctypes.c_int,
+                                    ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int]),
     "LzmaGpu_DeviceCount": (ctypes.c_int, []),
     "LzmaGpu_LastError": (ctypes.c_char_p, []),
     "LzmaGpu_Version": (ctypes.c_char_p, []),
@@ -854,6 +899,102 @@ def ppmd7_decode_batch_host(descs, n, src, dst, workspace_limit=0):
 
 
 # ---------------------------------------------------------------- streaming sessions
+
+# ---------------------------------------------------------------- LZMA encoding
+
+SZ_ERROR_OUTPUT_EOF = 7
+
+
+def enc_props(level=1, dict_size=0, lc=-1, lp=-1, pb=-1, fb=-1, mc=0, algo=-1, bt_mode=-1):
+    """A CLzmaEncProps after LzmaEncProps_Init with the given fields set."""
+    p = CLzmaEncProps()
+    _lib.LzmaEncProps_Init(ctypes.byref(p))
+    p.level, p.dictSize, p.lc, p.lp, p.pb, p.fb, p.mc = level, dict_size, lc, lp, pb, fb, mc
+    p.algo, p.btMode = algo, bt_mode
+    return p
+
+
+def enc_desc_from_props(props, end_mark=False):
+    """LzmaEncGpu_DescFromProps: (res, EncStreamDesc, props5)."""
+    d = EncStreamDesc()
+    props5 = ctypes.create_string_buffer(5)
+    r = _lib.LzmaEncGpu_DescFromProps(ctypes.byref(props), 1 if end_mark else 0, ctypes.byref(d),
+                                      props5)
+    return r, d, props5.raw
+
+
+def enc_plan(descs, n):
+    """LzmaEncGpu_PlanBatch: fills descs[i].ws_off; (res, order, workspace_bytes)."""
+    order = (ctypes.c_uint32 * max(n, 1))()
+    ws = ctypes.c_uint64(0)
+    r = _lib.LzmaEncGpu_PlanBatch(descs, n, order, ctypes.byref(ws))
+    return r, list(order)[:n], ws.value
+
+
+def encode_batch_device(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes=0, stream=0):
+    """LzmaEncGpu_EncodeBatch over raw device pointers (ints)."""
+    return _lib.LzmaEncGpu_EncodeBatch(d_descs, d_order or None, n, d_src, d_dst, d_ws, d_results,
+                                       lanes, stream or None)
+
+
+def encode_batch_host(descs, n, src, dst, workspace_limit=0):
+    """LzmaEncGpu_EncodeBatchHost: dst (bytes) is the output buffer's initial
+    contents.  Returns (res, results, dst bytes)."""
+    res = (EncResult * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.LzmaEncGpu_EncodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
+                                        workspace_limit)
+    return r, res, d.raw[:len(dst)]
+
+
+def encode_batch(items, level=1, dict_size=0, lc=-1, lp=-1, pb=-1, fb=-1, mc=0, end_mark=False):
+    """Encodes every bytes object of `items` with the same props in one host
+    batch.  Returns [(res, props5, packed)] per item; the capacity of each item
+    is len + len / 2 + 1024.  Props outside the fast path give
+    (SZ_ERROR_UNSUPPORTED or SZ_ERROR_PARAM, b"", b"") for every item."""
+    r, proto, props5 = enc_desc_from_props(enc_props(level, dict_size, lc, lp, pb, fb, mc), end_mark)
+    if r != SZ_OK:
+        return [(r, b"", b"")] * len(items)
+    n = len(items)
+    descs = (EncStreamDesc * max(n, 1))()
+    src_off = dst_off = 0
+    for i, it in enumerate(items):
+        ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(proto), ctypes.sizeof(proto))
+        cap = len(it) + len(it) // 2 + 1024
+        descs[i].src_off, descs[i].src_len, descs[i].dst_off, descs[i].dst_cap = (
+            src_off, len(it), dst_off, cap)
+        src_off += len(it)
+        dst_off += cap
+    r, res, out = encode_batch_host(descs, n, b"".join(bytes(it) for it in items), bytes(dst_off))
+    if r != SZ_OK:
+        return [(r, b"", b"")] * n
+    return [(res[i].res, props5, out[descs[i].dst_off:descs[i].dst_off + res[i].dest_len])
+            for i in range(n)]
+
+
+def LzmaEncode(src, props, dest_cap, end_mark=False, props_size=5):
+    """The drop-in: (res, destLen, props bytes, packed bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    pe = ctypes.create_string_buffer(8)
+    ps = ctypes.c_size_t(props_size)
+    res = _lib.LzmaEncode(d, ctypes.byref(dl), _buf(src), len(src), ctypes.byref(props), pe,
+                          ctypes.byref(ps), 1 if end_mark else 0, None, None, None)
+    ok = res in (SZ_OK, SZ_ERROR_OUTPUT_EOF)
+    return res, dl.value, pe.raw[:5], d.raw[:dl.value] if ok else b""
+
+
+def LzmaCompress(src, dest_cap, level=5, dict_size=0, lc=-1, lp=-1, pb=-1, fb=-1, num_threads=1):
+    """The drop-in: (res, destLen, props bytes, packed bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    pe = ctypes.create_string_buffer(8)
+    ps = ctypes.c_size_t(5)
+    res = _lib.LzmaCompress(d, ctypes.byref(dl), _buf(src), len(src), pe, ctypes.byref(ps), level,
+                            dict_size, lc, lp, pb, fb, num_threads)
+    ok = res in (SZ_OK, SZ_ERROR_OUTPUT_EOF)
+    return res, dl.value, pe.raw[:5], d.raw[:dl.value] if ok else b""
+
 
 def session_probs_bytes(props):
     return _lib.LzmaGpu_SessionProbsBytes(bytes(props), len(props))

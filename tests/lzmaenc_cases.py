@@ -1,0 +1,361 @@
+"""Cases, generators and reference access shared by the LZMA encoder tests
+(test_lzmaenc_emu.py, test_lzmaenc_gpu.py, test_lzmaenc_abi.py) and by
+tests/golden/make_golden_lzmaenc.py.
+
+A case is a dict of generator parameters (kind, seed, n), encoder props as the
+caller gives them (level, dict, lc, lp, pb, fb, mc, algo, bt; -1 / 0 = default),
+end_mark and cap.  cap is None (ample: n + n / 2 + 1024), an absolute capacity,
+or "full+K" / "full-K" relative to the size of the full stream.  Inputs are
+generated, never stored.  Expected results come from the live reference
+(oracle/_ref/libref_lzma.so) where it is built, else from
+tests/golden/lzmaenc_cases.json (sizes, SHA-256, first 32 bytes)."""
+import ctypes
+import hashlib
+import json
+import os
+import random
+import struct
+import subprocess
+
+import native
+
+GOLDEN = os.path.join(native.ROOT, "tests", "golden", "lzmaenc_cases.json")
+EMU_SRC = os.path.join(native.ROOT, "tests", "emu_lzmaenc", "lzmaenc_emu.cpp")
+CSRC = os.path.join(native.ROOT, "lzma-sdk-zliblike_amd", "csrc")
+OK, UNSUPPORTED, PARAM, OUTPUT_EOF = 0, 4, 5, 7
+KINDS = ("random", "text", "runs", "copy", "byte")
+_WORDS = [w.encode() for w in (
+    "the of and to in is that it was for on are as with his they at be this from have or by one "
+    "had not but what all were when we there can an your which their said if do will each about "
+    "how up out them then she many some so these would other into has more her two like him see "
+    "time could no make than first been its who now people my made over did down only way find "
+    "use may water long little very after words called just where most know").split()]
+
+
+def gen(kind, seed, n):
+    """n bytes of one of the data kinds, from incompressible to one repeated byte."""
+    rng = random.Random(seed)
+    if n == 0:
+        return b""
+    if kind == "random":
+        return rng.randbytes(n)
+    if kind == "byte":
+        return bytes([rng.randrange(256)]) * n
+    if kind == "text":
+        return b" ".join(rng.choices(_WORDS, k=n // 3 + 2))[:n]
+    if kind == "runs":
+        out = bytearray()
+        while len(out) < n:
+            out += bytes([rng.randrange(256)]) * rng.choice((1, 1, 2, 3, 5, 8, 40, 300, 700))
+        return bytes(out[:n])
+    if kind == "copy":      # random bytes and copies of earlier spans at any distance
+        out = bytearray(rng.randbytes(min(n, 16)))
+        while len(out) < n:
+            if rng.random() < 0.3:
+                out += rng.randbytes(rng.randrange(1, 24))
+            else:
+                at = rng.randrange(len(out))
+                ln = rng.choice((2, 3, 4, 5, 8, 20, 60, 300))
+                for i in range(ln):           # overlapping copies repeat, as a match does
+                    out.append(out[at + i])
+        return bytes(out[:n])
+    if kind == "period2":
+        return (bytes([rng.randrange(256), rng.randrange(256)]) * (n // 2 + 1))[:n]
+    if kind == "distant":   # a 2 KiB unique block that returns about 33 KiB later
+        block = rng.randbytes(2048)
+        text = b" ".join(rng.choices(_WORDS, k=n // 3 + 2))
+        return (block + text[:33 * 1024] + block + text[33 * 1024:])[:n]
+    if kind == "distant_ctl":  # the same with a different second block: the control
+        block = rng.randbytes(2048)
+        text = b" ".join(rng.choices(_WORDS, k=n // 3 + 2))
+        return (block + text[:33 * 1024] + random.Random(seed + 1).randbytes(2048)
+                + text[33 * 1024:])[:n]
+    raise ValueError(kind)
+
+
+def case(kind, seed, n, level=1, dict=0, lc=-1, lp=-1, pb=-1, fb=-1, mc=0, algo=-1, bt=-1,
+         end_mark=0, cap=None):
+    return {"kind": kind, "seed": seed, "n": n, "level": level, "dict": dict, "lc": lc, "lp": lp,
+            "pb": pb, "fb": fb, "mc": mc, "algo": algo, "bt": bt, "end_mark": end_mark, "cap": cap}
+
+
+def key(c):
+    return json.dumps(c, sort_keys=True)
+
+
+def data_of(c):
+    return gen(c["kind"], c["seed"], c["n"])
+
+
+def ample(n):
+    return n + n // 2 + 1024
+
+
+def edge_cases():
+    """The smallest shapes at which the encoder can go wrong."""
+    out = []
+    for n in range(7):                       # flush only, first byte, numAvail < 2, lenLimit < 4
+        for em in (0, 1):
+            out.append(case("text", 100 + n, n, end_mark=em))
+    for n in (273, 274, 600):                # the 273 extension, rep0 long, short rep
+        for fb in (5, 32, 273):
+            out.append(case("byte", 7, n, fb=fb))
+    out.append(case("period2", 8, 1000))
+    for n in (4095, 4096, 4097, 20000):      # ring wrap, delta >= cyclicBufferSize
+        out.append(case("text", 9, n, dict=4096))
+        out.append(case("copy", 10, n, dict=4096))
+    out.append(case("distant", 11, 40 * 1024, dict=1 << 16))
+    for cap in ("full+0", "full-1", 65536, 65535, 5, 0):   # the 64 KiB buffer flush, overflow
+        out.append(case("random", 12, 70 * 1024, dict=1 << 16, cap=cap))
+    for lc, lp, pb in ((0, 0, 0), (3, 0, 2), (0, 4, 4), (8, 4, 4)):
+        out.append(case("text", 13, 3000, lc=lc, lp=lp, pb=pb, end_mark=1))
+        out.append(case("copy", 14, 3000, lc=lc, lp=lp, pb=pb))
+    for mc in (1, 4, 48):
+        out.append(case("copy", 15, 6000, mc=mc))
+        out.append(case("text", 16, 6000, mc=mc, fb=64))
+    out.append(case("text", 17, 2000, fb=4))      # clamped to 5
+    out.append(case("runs", 18, 2000, fb=300))    # clamped to 273
+    out.append(case("text", 19, 500, level=5))    # the optimal parser: unsupported
+    out.append(case("text", 19, 500, algo=1))
+    out.append(case("text", 19, 500, bt=1))
+    out.append(case("text", 19, 500, lc=9))       # SZ_ERROR_PARAM
+    out.append(case("text", 19, 500, lp=5))
+    out.append(case("text", 19, 500, pb=5))
+    out.append(case("text", 19, 500, dict=(1 << 30) + 1))
+    out.append(case("text", 20, 5000, dict=5000))         # exactly dictSize, dictSize + 1
+    out.append(case("text", 20, 5001, dict=5000))
+    out.append(case("copy", 21, 3 << 11, dict=3 << 11))
+    out.append(case("copy", 21, (3 << 11) + 1, dict=3 << 11))
+    out.append(case("text", 22, 300, dict=1))             # the smallest dictionary
+    for level in (0, 2, 3, 4):
+        out.append(case("text", 23, 9000, level=level, dict=1 << 16))
+    return out
+
+
+def random_cases(count, seed, max_n=20000):
+    rng = random.Random(seed)
+    out = []
+    for _ in range(count):
+        lc, lp, pb = rng.choice(((-1, -1, -1), (0, 0, 0), (3, 0, 2), (0, 4, 4), (8, 4, 4),
+                                 (8, 0, 0), (0, 4, 0), (0, 0, 4), (4, 2, 1)))
+        n = rng.choice((rng.randrange(0, 40), rng.randrange(0, 600), rng.randrange(0, max_n + 1),
+                        rng.randrange(0, max_n + 1)))
+        cap = rng.choice((None, None, None, "full+0", "full-1", "full+3", 0, rng.randrange(0, 64),
+                          "full-%d" % rng.randrange(1, 40)))
+        out.append(case(rng.choice(KINDS), rng.randrange(1 << 30), n, level=rng.randrange(5),
+                        dict=rng.choice((4096, 5000, 3 << 11, 1 << 16)), lc=lc, lp=lp, pb=pb,
+                        fb=rng.choice((5, 6, 32, 64, 273)), end_mark=rng.randrange(2), cap=cap))
+    return out
+
+
+# ---------------------------------------------------------------- the live reference
+
+class CLzmaEncProps(ctypes.Structure):
+    _fields_ = [("level", ctypes.c_int), ("dictSize", ctypes.c_uint32), ("lc", ctypes.c_int),
+                ("lp", ctypes.c_int), ("pb", ctypes.c_int), ("algo", ctypes.c_int),
+                ("fb", ctypes.c_int), ("btMode", ctypes.c_int), ("numHashBytes", ctypes.c_int),
+                ("mc", ctypes.c_uint32), ("writeEndMark", ctypes.c_uint),
+                ("numThreads", ctypes.c_int)]
+
+
+_ALLOC = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+_FREE = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
+
+
+class ISzAlloc(ctypes.Structure):
+    _fields_ = [("Alloc", _ALLOC), ("Free", _FREE)]
+
+
+_libc = ctypes.CDLL(None)
+_libc.malloc.restype = ctypes.c_void_p
+_libc.malloc.argtypes = [ctypes.c_size_t]
+_libc.free.restype = None
+_libc.free.argtypes = [ctypes.c_void_p]
+_alloc = ISzAlloc(_ALLOC(lambda p, size: _libc.malloc(size) if size else None),
+                  _FREE(lambda p, addr: _libc.free(addr)))
+
+
+def props_of(c):
+    p = CLzmaEncProps()
+    native.ref().LzmaEncProps_Init(ctypes.byref(p))
+    p.level, p.dictSize, p.lc, p.lp, p.pb, p.fb = (c["level"], c["dict"], c["lc"], c["lp"],
+                                                   c["pb"], c["fb"])
+    p.mc, p.algo, p.btMode, p.numThreads = c["mc"], c["algo"], c["bt"], 1
+    return p
+
+
+def ref_normalize(c):
+    """LzmaEncProps_Normalize of the case's props by the reference itself."""
+    p = props_of(c)
+    native.ref().LzmaEncProps_Normalize(ctypes.byref(p))
+    return {f: getattr(p, f) for f, _ in CLzmaEncProps._fields_}
+
+
+def _ref_call(data, c, cap):
+    """The reference's LzmaEncode with the case's full CLzmaEncProps."""
+    lib = native.ref()
+    f = lib.LzmaEncode
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_char_p, native.size_t_p, ctypes.c_char_p, ctypes.c_size_t,
+                  ctypes.POINTER(CLzmaEncProps), ctypes.c_char_p, native.size_t_p, ctypes.c_int,
+                  ctypes.c_void_p, ctypes.POINTER(ISzAlloc), ctypes.POINTER(ISzAlloc)]
+    dst = ctypes.create_string_buffer(max(cap, 1))
+    dl = ctypes.c_size_t(cap)
+    props5 = ctypes.create_string_buffer(5)
+    ps = ctypes.c_size_t(5)
+    p = props_of(c)
+    res = f(dst, ctypes.byref(dl), data, len(data), ctypes.byref(p), props5, ctypes.byref(ps),
+            c["end_mark"], None, ctypes.byref(_alloc), ctypes.byref(_alloc))
+    if res in (PARAM,):
+        return res, 0, b"\0" * 5, b""
+    return res, dl.value, props5.raw, dst.raw[:dl.value]
+
+
+def _ref_shim(data, c, cap):
+    """ref_lzma_encode (the committed shim: no mc, algo or btMode)."""
+    lib = native.ref()
+    dst = ctypes.create_string_buffer(max(cap, 1))
+    dl = ctypes.c_size_t(cap)
+    props5 = ctypes.create_string_buffer(5)
+    res = lib.ref_lzma_encode(dst, ctypes.byref(dl), data, len(data), c["level"], c["dict"],
+                              c["lc"], c["lp"], c["pb"], c["fb"], c["end_mark"], props5)
+    if res == PARAM:
+        return res, 0, b"\0" * 5, b""
+    return res, dl.value, props5.raw, dst.raw[:dl.value]
+
+
+def resolve_cap(c, full_len):
+    cap = c["cap"]
+    if cap is None:
+        return ample(c["n"])
+    if isinstance(cap, str):
+        return max(0, full_len + int(cap[4:]))
+    return cap
+
+
+def ref_expect(c, data=None):
+    """(res, dest_len, props5, out, cap, full_len) of the case by the live
+    reference.  Props that do not select the fast path are the project's
+    documented difference: SZ_ERROR_UNSUPPORTED, nothing written -- decided from
+    the reference's own LzmaEncProps_Normalize."""
+    data = data_of(c) if data is None else data
+    nz = ref_normalize(c)
+    call = _ref_call if (c["mc"] or c["algo"] >= 0 or c["bt"] >= 0) else _ref_shim
+    param = nz["lc"] > 8 or nz["lp"] > 4 or nz["pb"] > 4 or nz["dictSize"] > (1 << 30)
+    if param:
+        res, dl, props5, out = call(data, c, 64)
+        assert res == PARAM
+        return PARAM, 0, b"\0" * 5, b"", 64, 0
+    if nz["algo"] != 0 or nz["btMode"] != 0:
+        return UNSUPPORTED, 0, b"\0" * 5, b"", 64, 0
+    full_len = 0
+    if isinstance(c["cap"], str):
+        r0 = call(data, c, ample(len(data)))
+        assert r0[0] == OK
+        full_len = r0[1]
+    cap = resolve_cap(c, full_len)
+    res, dl, props5, out = call(data, c, cap)
+    return res, dl, props5, out, cap, full_len
+
+
+# ---------------------------------------------------------------- goldens
+
+def sha(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def load_golden():
+    with open(GOLDEN) as f:
+        d = json.load(f)
+    d["by_key"] = {key(g["case"]): g for g in d["cases"]}
+    return d
+
+
+def golden_cases():
+    """The cases the golden file is generated over."""
+    return edge_cases() + random_cases(160, 20260)
+
+
+def expect(c, data=None, golden=None):
+    """What the reference gives for the case: live where the library is built,
+    else from the golden file (out is then None; compare len / sha256 / head).
+    Returns dict(res, dest_len, props5, cap, sha256, head, out)."""
+    if native.have_ref():
+        res, dl, props5, out, cap, _ = ref_expect(c, data)
+        return {"res": res, "dest_len": dl, "props5": props5, "cap": cap, "sha256": sha(out),
+                "head": out[:32], "out": out}
+    g = (golden or load_golden())["by_key"][key(c)]
+    return {"res": g["res"], "dest_len": g["dest_len"], "props5": bytes.fromhex(g["props5"]),
+            "cap": g["cap"], "sha256": g["sha256"], "head": bytes.fromhex(g["head"]), "out": None}
+
+
+def check(got, want, what):
+    """got = (res, dest_len, props5, out) against expect()'s dict."""
+    res, dl, props5, out = got
+    assert (res, dl) == (want["res"], want["dest_len"]), (what, res, dl, want["res"],
+                                                          want["dest_len"])
+    if res not in (PARAM, UNSUPPORTED):
+        assert props5 == want["props5"], (what, props5.hex(), want["props5"].hex())
+    assert len(out) == dl, what
+    if want["out"] is not None:
+        assert out == want["out"], what
+    else:
+        assert out[:32] == want["head"] and sha(out) == want["sha256"], what
+
+
+# ---------------------------------------------------------------- the emulator
+
+def build_emu(out_dir, extra=(), main=False, name=None):
+    out = os.path.join(str(out_dir), name or ("lzmaenc_emu_main" if main else "liblzmaenc_emu.so"))
+    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-I", CSRC]
+    cmd += (["-DLZMAENC_EMU_MAIN"] if main else ["-fPIC", "-shared"])
+    cmd += list(extra) if extra else ["-O2"]
+    subprocess.run(cmd + [EMU_SRC, "-o", out], check=True)
+    return out
+
+
+def load_emu(so):
+    lib = ctypes.CDLL(so)
+    f = lib.lzmaenc_emu_encode
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int,
+                  ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                  ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                  ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
+    lib.lzmaenc_emu_slice_bytes.restype = ctypes.c_uint64
+    lib.lzmaenc_emu_slice_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint64]
+    return lib
+
+
+def emu_encode(lib, data, c, cap, poison=0x3C):
+    dst = ctypes.create_string_buffer(b"\xEE" * (cap + 8), cap + 8)
+    props5 = ctypes.create_string_buffer(5)
+    dl = ctypes.c_uint64(0)
+    res = lib.lzmaenc_emu_encode(data, len(data), dst, cap, c["level"], c["dict"], c["lc"],
+                                 c["lp"], c["pb"], c["fb"], c["mc"], c["algo"], c["bt"],
+                                 c["end_mark"], poison, props5, ctypes.byref(dl))
+    assert dst.raw[cap:] == b"\xEE" * 8, "write past dst_cap"
+    return res, dl.value, props5.raw, dst.raw[:dl.value]
+
+
+def write_case_file(path, cases, golden=None):
+    """Records for the stand-alone build of lzmaenc_emu.cpp (sanitizer and
+    coverage runs).  Expected bytes come from the live reference where built,
+    else from the library build of the emulator, which the golden test pins."""
+    lib = None
+    with open(path, "wb") as f:
+        for c in cases:
+            data = data_of(c)
+            want = expect(c, data, golden)
+            out = want["out"]
+            if out is None:
+                if lib is None:
+                    lib = load_emu(build_emu(os.path.dirname(path), name="liblzmaenc_emu_dump.so"))
+                got = emu_encode(lib, data, c, want["cap"])
+                check(got, want, key(c))
+                out = got[3]
+            f.write(struct.pack("<iIiiiiIiii", c["level"], c["dict"], c["lc"], c["lp"], c["pb"],
+                                c["fb"], c["mc"], c["algo"], c["bt"], c["end_mark"]))
+            f.write(struct.pack("<QQiQ", len(data), want["cap"], want["res"], want["dest_len"]))
+            f.write(want["props5"] + data + out)
