@@ -32,6 +32,14 @@
  *       LzmaEncProps_GetDictSize replaces LzmaEnc.h:35 / LzmaEnc.c:76-81
  *       LzmaEncode              replaces LzmaEnc.h:72-74 / LzmaEnc.c:2248-2268
  *       LzmaCompress            replaces LzmaLib.h:98-107 / LzmaLib.c:15-38
+ *       Lzma2EncProps_Init      replaces Lzma2Enc.h:21 / Lzma2Enc.c:168-174
+ *       Lzma2EncProps_Normalize replaces Lzma2Enc.h:22 / Lzma2Enc.c:176-234
+ *       Lzma2Enc_Create         replaces Lzma2Enc.h:38 / Lzma2Enc.c:367-387
+ *       Lzma2Enc_Destroy        replaces Lzma2Enc.h:39 / Lzma2Enc.c:389-409
+ *       Lzma2Enc_SetProps       replaces Lzma2Enc.h:40 / Lzma2Enc.c:411-421
+ *       Lzma2Enc_WriteProperties replaces Lzma2Enc.h:41 / Lzma2Enc.c:423-432
+ *       Lzma2Enc_Encode         replaces Lzma2Enc.h:42-43 / Lzma2Enc.c:434-477
+ *                               (differences: at its declaration below)
  *
  *     Encoding covers the reference's fast path only (algo 0 with the hash-chain
  *     finder, what levels 0..4 select): the output is the reference's, bit for
@@ -926,6 +934,115 @@ SRes LzmaEncode(Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
 int LzmaCompress(unsigned char *dest, size_t *destLen, const unsigned char *src, size_t srcLen,
                  unsigned char *outProps, size_t *outPropsSize, int level, unsigned dictSize,
                  int lc, int lp, int pb, int fb, int numThreads);
+
+/* ---------------------------------------------------------------- LZMA2 and xz writers */
+
+/* LZMA2 in the reference's multi-threaded layout (Lzma2Enc.c:310-361): the
+ * input is cut into blockSize pieces, every piece is an independent run of
+ * chunks that starts with a dictionary reset, the runs are concatenated and one
+ * 0x00 ends the stream.  A piece is one lane of an encode batch
+ * (csrc/lzma2enc_device.h), on the fast path only (levels 0..4).  Per block the
+ * outcome is MtCallbackImp_Code's over a buffer of dst_cap bytes, without the
+ * final 0x00:
+ *   SZ_OK                 dest_len bytes of chunks written; with dst_cap >=
+ *                         Lzma2EncGpu_BlockBound(src_len) they are the bytes of
+ *                         the reference's single-threaded Lzma2Enc_Encode of the
+ *                         block alone, minus its last byte
+ *   SZ_ERROR_OUTPUT_EOF   a chunk did not fit: dest_len = the bytes of the whole
+ *                         chunks before it; bytes in [dest_len, dst_cap) are
+ *                         unspecified
+ *   SZ_ERROR_PARAM        what LzmaEncGpu_EncodeBatch refuses, and lc + lp > 4
+ *   SZ_ERROR_UNSUPPORTED  src_len >= 2^31
+ * Bytes of d_dst outside [dst_off, dst_off + dst_cap) are never written.  The
+ * descriptors and results are the LZMA encoder's (write_end_mark is ignored). */
+
+#ifndef __LZMA2_ENC_H
+typedef struct {   /* 64 bytes, Lzma2Enc.h:13-19 */
+  CLzmaEncProps lzmaProps;
+  size_t blockSize;
+  int numBlockThreads;
+  int numTotalThreads;
+} CLzma2EncProps;
+typedef void *CLzma2EncHandle;
+#endif
+#ifndef __7Z_TYPES_H
+typedef struct {   /* Types.h:137-160 */
+  SRes (*Read)(void *p, void *buf, size_t *size);
+  /* if (input(*size) != 0 && output(*size) == 0) means end_of_stream.
+     (output(*size) < input(*size)) is allowed */
+} ISeqInStream;
+typedef struct {
+  size_t (*Write)(void *p, const void *buf, size_t size);
+  /* Returns: result - the number of actually written bytes.
+     (result < size) means error */
+} ISeqOutStream;
+#endif
+
+/* Lzma2Enc.c:168-234, of a build with threads (NUM_MT_CODER_THREADS_MAX 32) */
+void Lzma2EncProps_Init(CLzma2EncProps *p);
+void Lzma2EncProps_Normalize(CLzma2EncProps *p);
+
+/* src_len + (src_len >> 10) + 16: the reference's destBlockSize (:471) */
+size_t Lzma2EncGpu_BlockBound(size_t src_len);
+/* Host only.  Lzma2Enc_SetProps' check (lc + lp > 4: SZ_ERROR_PARAM), then
+ * LzmaEncGpu_DescFromProps' over the normalised lzmaProps.  On SZ_OK the props
+ * fields of *desc are set and *prop is Lzma2Enc_WriteProperties' byte. */
+SRes Lzma2EncGpu_DescFromProps(const CLzma2EncProps *props, LzmaEncGpuStreamDesc *desc, Byte *prop);
+/* LzmaEncGpu_PlanBatch over the LZMA2 slices (the LZMA slice plus the table
+ * that holds the saved probability cells of the chunk in flight). */
+SRes Lzma2EncGpu_PlanBatch(LzmaEncGpuStreamDesc *descs, size_t n, uint32_t *order,
+                           uint64_t *workspace_bytes);
+/* LzmaEncGpu_EncodeBatch's contract with blocks for streams. */
+SRes Lzma2EncGpu_EncodeBatch(const LzmaEncGpuStreamDesc *d_descs, const uint32_t *d_order,
+                             size_t n, const Byte *d_src, Byte *d_dst, void *d_workspace,
+                             LzmaEncGpuResult *d_results, unsigned lanes, void *stream);
+/* LzmaEncGpu_EncodeBatchHost's contract with blocks for streams. */
+SRes Lzma2EncGpu_EncodeBatchHost(const LzmaEncGpuStreamDesc *descs, size_t n, const Byte *src,
+                                 size_t src_size, Byte *dst, size_t dst_size,
+                                 LzmaEncGpuResult *results, uint64_t workspace_limit);
+/* One stream from the blocks of a finished batch, on the device: d_offsets[i]
+ * (n + 1 entries of scratch) = the sum of d_results[0, i).dest_len, block i's
+ * bytes go from d_slots + d_descs[i].dst_off to d_out + d_offsets[i], and 0x00
+ * follows the last.  d_total: res = the first block's that is not SZ_OK (_pad =
+ * its index), else SZ_ERROR_OUTPUT_EOF when the stream is longer than out_cap,
+ * else SZ_OK; dest_len = the stream's length.  d_out is written only on SZ_OK.
+ * All pointers device memory; asynchronous on `stream`; d_slots and d_out may
+ * not overlap. */
+SRes Lzma2EncGpu_Compact(const LzmaEncGpuStreamDesc *d_descs, const LzmaEncGpuResult *d_results,
+                         size_t n, const Byte *d_slots, Byte *d_out, uint64_t out_cap,
+                         uint64_t *d_offsets, LzmaEncGpuResult *d_total, void *stream);
+/* One host buffer as one LZMA2 stream: cut by props->blockSize (after
+ * Lzma2EncProps_Normalize), upload, one batch, compaction, download.  *destLen
+ * in: capacity, out: the stream's length; *prop = the dictionary byte.  An empty
+ * source gives the byte 00.  SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED as
+ * Lzma2EncGpu_DescFromProps (and a source of 2^31 blocks or more),
+ * SZ_ERROR_OUTPUT_EOF when dest is short, SZ_ERROR_FAIL without a device. */
+SRes LzmaGpu_Lzma2EncodeHost(Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
+                             const CLzma2EncProps *props, Byte *prop);
+
+/* Lzma2Enc.h:36-43.  Differences from the reference: Lzma2Enc_Encode reads the
+ * input stream to its end before it encodes; numBlockThreads only selects the
+ * layout (<= 1: the whole input is one block, the reference's
+ * Lzma2Enc_EncodeMt1; > 1: blocks of blockSize); progress is called once per
+ * finished block, after its bytes went through outStream; props off the fast
+ * path give SZ_ERROR_UNSUPPORTED; alloc only holds the handle. */
+CLzma2EncHandle Lzma2Enc_Create(ISzAlloc *alloc, ISzAlloc *allocBig);
+void Lzma2Enc_Destroy(CLzma2EncHandle p);
+SRes Lzma2Enc_SetProps(CLzma2EncHandle p, const CLzma2EncProps *props);
+Byte Lzma2Enc_WriteProperties(CLzma2EncHandle p);
+SRes Lzma2Enc_Encode(CLzma2EncHandle p, ISeqOutStream *outStream, ISeqInStream *inStream,
+                     ICompressProgress *progress);
+
+/* One xz stream from a host buffer: every piece of blockSize bytes is one xz
+ * block with the filter chain LZMA2 only (a block header without size fields,
+ * as Xz_Encode writes it, XzEnc.c:41-160), its data the piece's chunks and
+ * 0x00.  The blocks are one encode batch; the block checks (LZMA_GPU_XZ_CHECK_*)
+ * are computed on the device over the source pieces; headers, index and footer
+ * are written on the host.  An empty source gives the 32-byte empty stream.
+ * SZ_ERROR_UNSUPPORTED for another check id, SZ_ERROR_OUTPUT_EOF when dest is
+ * short, else as LzmaGpu_Lzma2EncodeHost. */
+SRes LzmaGpu_XzEncode(Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
+                      const CLzma2EncProps *props, unsigned check_type);
 
 /* ---- 7z archives as folder batches ----------------
  * Replaces SzArEx_Open (7zIn.c:1314) + a SzArEx_Extract loop over every file

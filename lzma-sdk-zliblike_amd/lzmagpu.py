@@ -10,7 +10,9 @@ There is no fallback: if lib/liblzmagpu.so is missing this module raises at
 import time, and on a machine without a HIP device every decode and encode
 returns SZ_ERROR_FAIL (``LzmaGpu_LastError`` says why).  Encoding (the
 reference's fast path, levels 0..4): ``encode_batch``, ``LzmaEncode``,
-``LzmaCompress`` and the ``LzmaEncGpu_*`` batch calls.
+``LzmaCompress`` and the ``LzmaEncGpu_*`` batch calls; LZMA2 and xz writing over
+them: ``lzma2_encode_batch``, ``lzma2_compress``, ``xz_compress`` and the
+``Lzma2Enc_*`` drop-ins.
 """
 import ctypes
 import os
@@ -194,6 +196,30 @@ class CLzmaEncProps(ctypes.Structure):
                 ("numThreads", ctypes.c_int)]
 
 
+class CLzma2EncProps(ctypes.Structure):
+    """CLzma2EncProps (Lzma2Enc.h:13-19)."""
+    _fields_ = [("lzmaProps", CLzmaEncProps), ("blockSize", ctypes.c_size_t),
+                ("numBlockThreads", ctypes.c_int), ("numTotalThreads", ctypes.c_int)]
+
+
+SeqRead = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                           ctypes.POINTER(ctypes.c_size_t))
+SeqWrite = ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+ProgressFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
+
+
+class ISeqInStream(ctypes.Structure):
+    _fields_ = [("Read", SeqRead)]
+
+
+class ISeqOutStream(ctypes.Structure):
+    _fields_ = [("Write", SeqWrite)]
+
+
+class ICompressProgress(ctypes.Structure):
+    _fields_ = [("Progress", ProgressFn)]
+
+
 class EncStreamDesc(ctypes.Structure):
     """LzmaEncGpuStreamDesc (include/lzma_gpu.h): one stream of an encode batch."""
     _fields_ = [("src_off", ctypes.c_uint64), ("src_len", ctypes.c_uint64),
@@ -337,6 +363,32 @@ _sig = {
     "LzmaCompress": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, _P, _sp, ctypes.c_int,
                                     ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int]),
+    "Lzma2EncProps_Init": (None, [ctypes.POINTER(CLzma2EncProps)]),
+    "Lzma2EncProps_Normalize": (None, [ctypes.POINTER(CLzma2EncProps)]),
+    "Lzma2EncGpu_BlockBound": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "Lzma2EncGpu_DescFromProps": (ctypes.c_int, [ctypes.POINTER(CLzma2EncProps),
+                                                 ctypes.POINTER(EncStreamDesc),
+                                                 ctypes.POINTER(ctypes.c_ubyte)]),
+    "Lzma2EncGpu_PlanBatch": (ctypes.c_int, [ctypes.POINTER(EncStreamDesc), ctypes.c_size_t, _P,
+                                             ctypes.POINTER(ctypes.c_uint64)]),
+    "Lzma2EncGpu_EncodeBatch": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P,
+                                               ctypes.c_uint, _P]),
+    "Lzma2EncGpu_EncodeBatchHost": (ctypes.c_int, [ctypes.POINTER(EncStreamDesc), ctypes.c_size_t,
+                                                   _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                   ctypes.POINTER(EncResult), ctypes.c_uint64]),
+    "Lzma2EncGpu_Compact": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, ctypes.c_uint64, _P, _P,
+                                           _P]),
+    "LzmaGpu_Lzma2EncodeHost": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t,
+                                               ctypes.POINTER(CLzma2EncProps),
+                                               ctypes.POINTER(ctypes.c_ubyte)]),
+    "Lzma2Enc_Create": (ctypes.c_void_p, [ctypes.POINTER(ISzAlloc), ctypes.POINTER(ISzAlloc)]),
+    "Lzma2Enc_Destroy": (None, [ctypes.c_void_p]),
+    "Lzma2Enc_SetProps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CLzma2EncProps)]),
+    "Lzma2Enc_WriteProperties": (ctypes.c_ubyte, [ctypes.c_void_p]),
+    "Lzma2Enc_Encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ISeqOutStream),
+                                       ctypes.POINTER(ISeqInStream), _P]),
+    "LzmaGpu_XzEncode": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t,
+                                        ctypes.POINTER(CLzma2EncProps), ctypes.c_uint]),
     "LzmaGpu_DeviceCount": (ctypes.c_int, []),
     "LzmaGpu_LastError": (ctypes.c_char_p, []),
     "LzmaGpu_Version": (ctypes.c_char_p, []),
@@ -994,6 +1046,129 @@ def LzmaCompress(src, dest_cap, level=5, dict_size=0, lc=-1, lp=-1, pb=-1, fb=-1
                             dict_size, lc, lp, pb, fb, num_threads)
     ok = res in (SZ_OK, SZ_ERROR_OUTPUT_EOF)
     return res, dl.value, pe.raw[:5], d.raw[:dl.value] if ok else b""
+
+
+# ---------------------------------------------------------------- LZMA2 and xz writing
+
+def enc2_props(level=1, dict_size=0, lc=-1, lp=-1, pb=-1, block_size=0, block_threads=-1,
+               total_threads=-1, lzma_threads=-1):
+    """A CLzma2EncProps after Lzma2EncProps_Init with the given fields set."""
+    p = CLzma2EncProps()
+    _lib.Lzma2EncProps_Init(ctypes.byref(p))
+    q = p.lzmaProps
+    q.level, q.dictSize, q.lc, q.lp, q.pb, q.numThreads = level, dict_size, lc, lp, pb, lzma_threads
+    p.blockSize, p.numBlockThreads, p.numTotalThreads = block_size, block_threads, total_threads
+    return p
+
+
+def block_bound(n):
+    return _lib.Lzma2EncGpu_BlockBound(n)
+
+
+def enc2_desc_from_props(props):
+    """Lzma2EncGpu_DescFromProps: (res, EncStreamDesc, prop byte)."""
+    d = EncStreamDesc()
+    prop = ctypes.c_ubyte(0)
+    r = _lib.Lzma2EncGpu_DescFromProps(ctypes.byref(props), ctypes.byref(d), ctypes.byref(prop))
+    return r, d, prop.value
+
+
+def enc2_plan(descs, n):
+    """Lzma2EncGpu_PlanBatch: fills descs[i].ws_off; (res, order, workspace_bytes)."""
+    order = (ctypes.c_uint32 * max(n, 1))()
+    ws = ctypes.c_uint64(0)
+    r = _lib.Lzma2EncGpu_PlanBatch(descs, n, order, ctypes.byref(ws))
+    return r, list(order)[:n], ws.value
+
+
+def lzma2_encode_batch_device(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes=0,
+                              stream=0):
+    """Lzma2EncGpu_EncodeBatch over raw device pointers (ints)."""
+    return _lib.Lzma2EncGpu_EncodeBatch(d_descs, d_order or None, n, d_src, d_dst, d_ws, d_results,
+                                        lanes, stream or None)
+
+
+def lzma2_compact_device(d_descs, d_results, n, d_slots, d_out, out_cap, d_offsets, d_total,
+                         stream=0):
+    """Lzma2EncGpu_Compact over raw device pointers (ints)."""
+    return _lib.Lzma2EncGpu_Compact(d_descs, d_results, n, d_slots, d_out, out_cap, d_offsets,
+                                    d_total, stream or None)
+
+
+def lzma2_encode_batch_host(descs, n, src, dst, workspace_limit=0):
+    """Lzma2EncGpu_EncodeBatchHost: dst (bytes) is the output buffer's initial
+    contents.  Returns (res, results, dst bytes)."""
+    res = (EncResult * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.Lzma2EncGpu_EncodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
+                                         workspace_limit)
+    return r, res, d.raw[:len(dst)]
+
+
+def lzma2_encode_batch(items, level=1, dict_size=0, lc=-1, lp=-1, pb=-1):
+    """Encodes every bytes object of `items` as one LZMA2 block (chunks from a
+    dictionary reset on, no final 0x00) with the same props in one host batch.
+    Returns [(res, prop, packed)] per item; each item's capacity is its block
+    bound."""
+    r, proto, prop = enc2_desc_from_props(enc2_props(level, dict_size, lc, lp, pb))
+    if r != SZ_OK:
+        return [(r, 0, b"")] * len(items)
+    n = len(items)
+    descs = (EncStreamDesc * max(n, 1))()
+    src_off = dst_off = 0
+    for i, it in enumerate(items):
+        ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(proto), ctypes.sizeof(proto))
+        cap = block_bound(len(it))
+        descs[i].src_off, descs[i].src_len, descs[i].dst_off, descs[i].dst_cap = (
+            src_off, len(it), dst_off, cap)
+        src_off += len(it)
+        dst_off += cap
+    r, res, out = lzma2_encode_batch_host(descs, n, b"".join(bytes(it) for it in items),
+                                          bytes(dst_off))
+    if r != SZ_OK:
+        return [(r, 0, b"")] * n
+    return [(res[i].res, prop, out[descs[i].dst_off:descs[i].dst_off + res[i].dest_len])
+            for i in range(n)]
+
+
+def Lzma2EncodeHost(src, props, dest_cap):
+    """LzmaGpu_Lzma2EncodeHost: (res, prop byte, stream bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    prop = ctypes.c_ubyte(0)
+    r = _lib.LzmaGpu_Lzma2EncodeHost(d, ctypes.byref(dl), _buf(src), len(src), ctypes.byref(props),
+                                     ctypes.byref(prop))
+    return r, prop.value, d.raw[:dl.value] if r == SZ_OK else b""
+
+
+def lzma2_compress(data, level=1, dict_size=0, block_size=0, lc=-1, lp=-1, pb=-1):
+    """One LZMA2 stream (blocks of block_size, 0 = the reference's default) and
+    its dictionary byte: (prop, bytes).  Raises on an error."""
+    bs = block_size or (1 << 20)    # the default block is 1 MiB or more
+    cap = len(data) + 1 + (len(data) // bs + 1) * (block_bound(bs) - bs)
+    r, prop, out = Lzma2EncodeHost(data, enc2_props(level, dict_size, lc, lp, pb, block_size), cap)
+    if r != SZ_OK:
+        raise RuntimeError(f"LzmaGpu_Lzma2EncodeHost: {r}: {last_error()}")
+    return prop, out
+
+
+def XzEncode(src, props, check, dest_cap):
+    """LzmaGpu_XzEncode: (res, file bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    r = _lib.LzmaGpu_XzEncode(d, ctypes.byref(dl), _buf(src), len(src), ctypes.byref(props), check)
+    return r, d.raw[:dl.value] if r == SZ_OK else b""
+
+
+def xz_compress(data, check=1, level=1, dict_size=0, block_size=0, lc=-1, lp=-1, pb=-1):
+    """One xz stream, a block per block_size bytes.  Raises on an error."""
+    bs = block_size or (1 << 20)
+    blocks = len(data) // bs + 1
+    cap = 64 + len(data) + blocks * (block_bound(bs) - bs + 12 + 4 + 32 + 20)
+    r, out = XzEncode(data, enc2_props(level, dict_size, lc, lp, pb, block_size), check, cap)
+    if r != SZ_OK:
+        raise RuntimeError(f"LzmaGpu_XzEncode: {r}: {last_error()}")
+    return out
 
 
 def session_probs_bytes(props):

@@ -1,0 +1,366 @@
+"""Cases, generators and reference access shared by the LZMA2 encoder tests
+(test_lzma2enc_emu.py, test_lzma2enc_gpu.py, test_lzma2enc_abi.py) and by
+tests/golden/make_golden_lzma2enc.py.
+
+A case is a list of (kind, seed, n) segments for native.gen, concatenated, plus
+the props a caller sets (level, dict, lc, lp, pb).  Inputs are generated, never
+stored.  The expected bytes are the reference's single-threaded Lzma2Enc_Encode
+of the case as one block (native.ref()'s ref_lzma2_encode) -- live where
+oracle/_ref/libref_lzma.so is built, else tests/golden/lzma2enc_cases.json
+(length, SHA-256, first 32 bytes, prop byte and the chunk list).  The block
+encoder gives those bytes without the final 0x00, which the framing adds."""
+import ctypes
+import hashlib
+import json
+import lzma
+import os
+import random
+import struct
+import subprocess
+
+import native
+
+GOLDEN = os.path.join(native.ROOT, "tests", "golden", "lzma2enc_cases.json")
+EMU_SRC = os.path.join(native.ROOT, "tests", "emu_lzma2enc", "lzma2enc_emu.cpp")
+CSRC = os.path.join(native.ROOT, "lzma-sdk-zliblike_amd", "csrc")
+OK, UNSUPPORTED, PARAM, OUTPUT_EOF, FAIL = 0, 4, 5, 7, 11
+MIB = 1 << 20
+
+# (level, dictSize, blockSize, numBlockThreads, numTotalThreads, lzmaProps.numThreads) ->
+# (lzmaProps.numThreads, numBlockThreads, numTotalThreads, blockSize, dictSize), worked out
+# by hand from Lzma2Enc.c:176-234 and LzmaEnc.c:53-74 of a build with threads
+NORMALIZE = [
+    ((1, 0, 0, -1, -1, -1), (1, 1, 1, MIB, 1 << 16)),
+    ((5, 0, 0, -1, -1, -1), (2, 1, 2, 1 << 26, 1 << 24)),
+    ((1, 0, 0, 0, 0, -1), (1, 1, 1, MIB, 1 << 16)),
+    ((1, 0, 0, 33, -1, -1), (1, 32, 32, MIB, 1 << 16)),       # numBlockThreads 33 -> 32
+    ((1, 0, 0, 4, -1, -1), (1, 4, 4, MIB, 1 << 16)),
+    ((5, 0, 0, -1, 8, -1), (2, 4, 8, 1 << 26, 1 << 24)),      # t2 = t3 / t1n
+    ((5, 0, 0, -1, 1, -1), (1, 1, 1, 1 << 26, 1 << 24)),      # t3 / t1n == 0
+    ((1, 0, 0, -1, 100, -1), (1, 32, 100, MIB, 1 << 16)),     # capped after the division
+    ((1, 0, 0, 4, 8, -1), (2, 4, 8, MIB, 1 << 16)),           # t1 = t3 / t2
+    ((1, 0, 0, 4, 2, -1), (1, 4, 2, MIB, 1 << 16)),           # t3 / t2 == 0
+    ((1, 0, 0, 4, 5, 2), (2, 4, 8, MIB, 1 << 16)),            # all given: t3 = t1n * t2
+    ((1, 4096, 0, -1, -1, -1), (1, 1, 1, MIB, 4096)),         # max(1 MiB, 4 * dict)
+    ((1, MIB, 0, -1, -1, -1), (1, 1, 1, 4 * MIB, MIB)),
+    ((4, 0, 0, -1, -1, -1), (1, 1, 1, 16 * MIB, 4 * MIB)),
+    ((0, 0, 0, -1, -1, -1), (1, 1, 1, MIB, 1 << 14)),
+    ((1, 1 << 28, 0, -1, -1, -1), (1, 1, 1, 1 << 28, 1 << 28)),   # capped at 256 MiB
+    ((1, 1 << 30, 0, -1, -1, -1), (1, 1, 1, 1 << 30, 1 << 30)),   # never below the dictionary
+    ((1, 0, 12345, 2, -1, -1), (1, 2, 2, 12345, 1 << 16)),        # a given block size stays
+]
+
+
+def case(segs, level=1, dict=1 << 16, lc=3, lp=0, pb=2):
+    return {"segs": [list(s) for s in segs], "level": level, "dict": dict, "lc": lc, "lp": lp,
+            "pb": pb}
+
+
+def key(c):
+    return json.dumps(c, sort_keys=True)
+
+
+def size_of(c):
+    return sum(s[2] for s in c["segs"])
+
+
+_data = {}
+
+
+def data_of(c):
+    k = json.dumps(c["segs"])
+    if k not in _data:
+        if len(_data) > 64:
+            _data.clear()
+        _data[k] = b"".join(native.gen(kind, seed, n) for kind, seed, n in c["segs"])
+    return _data[k]
+
+
+def block_bound(n):
+    """Lzma2EncGpu_BlockBound: the reference's destBlockSize (Lzma2Enc.c:471)."""
+    return n + (n >> 10) + 16
+
+
+# the chunk pattern each shape was chosen for, at level 1, dict 64 KiB, lc3 lp0 pb2
+PATTERN_CASES = [
+    case([]),                                              # 00
+    case([("text", 1, 1)]),                                # copy-reset(1)
+    case([("text", 1, 300000)]),                           # the pack limit; 21-bit unpack field
+    case([("random", 2, 60000)]),                          # restore, a second failed attempt
+    case([("random", 3, 58000), ("text", 4, 40000)]),      # first LZMA chunk after a copy: mode 2
+    case([("text", 5, 40000), ("random", 6, 70000)]),      # LZMA, then copy
+    case([("text", 20, 160000), ("random", 21, 57000), ("text", 22, 40000)]),  # restore, go on
+]
+# the unpack limit: mode 3 (2,092,927 -> 12,211), mode 0.  Emulator only.
+UNPACK_LIMIT_CASE = case([("runs", 8, 3 * MIB)])
+
+
+def edge_cases():
+    """The smallest shapes found for each path, then the props corners."""
+    out = list(PATTERN_CASES)
+    for n in (2, 3, 4, 5):
+        out.append(case([("text", 30 + n, n)]))
+    for level in (0, 2, 3, 4):
+        out.append(case([("text", 40, 9000), ("runs", 41, 3000)], level=level))
+        out.append(case([("text", 40, 30000)], level=level, dict=0))   # the level's dictionary
+    for d in (4096, MIB):
+        out.append(case([("text", 42, 70000)], dict=d))
+        out.append(case([("random", 43, 5000), ("text", 44, 9000)], dict=d))
+    for lc, lp in ((4, 0), (0, 4), (1, 3), (2, 2), (0, 0)):
+        out.append(case([("text", 45, 6000), ("runs", 46, 2000)], lc=lc, lp=lp))
+    for pb in (0, 4):
+        out.append(case([("text", 47, 6000), ("runs", 48, 2000)], pb=pb))
+    for lc, lp in ((4, 1), (3, 2), (1, 4), (5, 0)):        # lc + lp = 5: SZ_ERROR_PARAM
+        out.append(case([("text", 49, 500)], lc=lc, lp=lp))
+    out.append(case([("text", 49, 500)], lc=4, lp=1, level=5))   # the lc + lp check comes first
+    return out
+
+
+def random_cases(count, seed, max_n=None):
+    rng = random.Random(seed)
+    out = []
+    for _ in range(count):
+        top = rng.choice((40, 600, 20000, 20000, 200 * 1024, 200 * 1024))
+        if rng.random() < 0.02:
+            top = 400 * 1024
+        if max_n is not None:
+            top = min(top, max_n)
+        total = rng.randrange(0, top + 1)
+        segs = []
+        for _ in range(rng.choice((1, 1, 2, 3, 4))):
+            n = rng.randrange(0, total + 1) if total else 0
+            if n:
+                segs.append((rng.choice(("text", "random", "runs")), rng.randrange(1 << 30), n))
+            total -= n
+        lc, lp, pb = rng.choice(((3, 0, 2), (3, 0, 2), (0, 0, 0), (4, 0, 4), (0, 4, 0), (2, 2, 1),
+                                 (1, 3, 3)))
+        out.append(case(segs, level=rng.randrange(5), dict=rng.choice((4096, 1 << 16, 1 << 16, MIB)),
+                        lc=lc, lp=lp, pb=pb))
+    return out
+
+
+def golden_cases():
+    """The cases the golden file is generated over."""
+    return edge_cases() + [UNPACK_LIMIT_CASE] + random_cases(120, 20261)
+
+
+# one buffer cut into blocks (LzmaGpu_Lzma2EncodeHost, LzmaGpu_XzEncode): the case and
+# the block size
+MULTIBLOCK = [
+    (case([("text", 50, 300000), ("random", 51, 70000)]), 100000),
+    (case([("text", 52, 250000)]), 65536),
+    (case([("text", 42, 70000)], dict=4096), 20000),
+]
+
+
+# ---------------------------------------------------------------- the reference
+
+def ref_stream(c, data=None, block_size=0):
+    """(res, prop, out) of the reference's Lzma2Enc_Encode (one thread) over the
+    case: its chunks and the final 0x00."""
+    data = data_of(c) if data is None else data
+    lib = native.ref()
+    cap = len(data) + len(data) // 2 + 4096
+    dst = ctypes.create_string_buffer(cap)
+    dl = ctypes.c_size_t(cap)
+    prop = ctypes.c_ubyte(0)
+    res = lib.ref_lzma2_encode(dst, ctypes.byref(dl), data, len(data), c["level"], c["dict"],
+                               c["lc"], c["lp"], c["pb"], block_size, ctypes.byref(prop))
+    if res != OK:
+        return res, 0, b""
+    return res, prop.value, dst.raw[:dl.value]
+
+
+def ref_multiblock(c, block):
+    """The reference's multi-threaded layout built from its single-threaded
+    encoder, as make_golden.lzma2_multiblock builds it: every block's stream
+    without its final 0x00, concatenated, then 0x00.  (prop, [block bytes])."""
+    data, prop, parts = data_of(c), 0, []
+    for at in range(0, len(data), block):
+        res, prop, out = ref_stream(c, data[at:at + block])
+        assert res == OK and out[-1] == 0
+        parts.append(out[:-1])
+    return prop, parts
+
+
+def multiblock_record(c, block, prop, parts):
+    whole = b"".join(parts) + b"\0"
+    return {"case": c, "block": block, "prop": prop, "len": len(whole), "sha256": sha(whole),
+            "blocks": [{"len": len(p), "sha256": sha(p)} for p in parts]}
+
+
+def expect_multiblock(c, block, golden=None):
+    """multiblock_record of the live reference where built, else the golden's."""
+    if native.have_ref():
+        prop, parts = ref_multiblock(c, block)
+        return multiblock_record(c, block, prop, parts)
+    for m in (golden or load_golden())["multiblock"]:
+        if key(m["case"]) == key(c) and m["block"] == block:
+            return m
+    raise KeyError(key(c))
+
+
+def parse_chunks(out):
+    """[(control, unpack, pack)] of an LZMA2 stream; the final 0x00 is (0, 0, 0).
+    Stops where the bytes end."""
+    chunks, at = [], 0
+    while at < len(out):
+        ctl = out[at]
+        if ctl == 0:
+            chunks.append((0, 0, 0))
+            at += 1
+            break
+        assert ctl in (1, 2) or ctl >= 0x80, ctl
+        if ctl < 0x80:
+            n = ((out[at + 1] << 8) | out[at + 2]) + 1
+            chunks.append((ctl, n, n))
+            at += 3 + n
+        else:
+            u = (((ctl & 0x1F) << 16) | (out[at + 1] << 8) | out[at + 2]) + 1
+            p = ((out[at + 3] << 8) | out[at + 4]) + 1
+            chunks.append((ctl & 0xE0, u, p))
+            at += 5 + (1 if ctl >= 0xC0 else 0) + p
+    assert at == len(out), (at, len(out))
+    return chunks
+
+
+def chunk_sizes(out):
+    """Byte length of every chunk of an LZMA2 stream, in order."""
+    sizes = []
+    for ctl, _, p in parse_chunks(out):
+        sizes.append(1 if ctl == 0 else 3 + p if ctl < 0x80 else 5 + (1 if ctl >= 0xC0 else 0) + p)
+    return sizes
+
+
+def decode_raw(out, prop):
+    """Python's lzma over a whole LZMA2 stream (chunks and the final 0x00)."""
+    d = 0xFFFFFFFF if prop == 40 else (2 | (prop & 1)) << (prop // 2 + 11)
+    return lzma.decompress(out, format=lzma.FORMAT_RAW,
+                           filters=[{"id": lzma.FILTER_LZMA2, "dict_size": d}])
+
+
+# ---------------------------------------------------------------- goldens
+
+def sha(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def record(c, res, prop, out):
+    return {"case": c, "res": res, "prop": prop, "len": len(out), "sha256": sha(out),
+            "head": out[:32].hex(), "chunks": [list(t) for t in parse_chunks(out)]}
+
+
+def load_golden():
+    with open(GOLDEN) as f:
+        d = json.load(f)
+    d["by_key"] = {key(g["case"]): g for g in d["cases"]}
+    return d
+
+
+def expect(c, data=None, golden=None):
+    """The reference's record of the case (live where built, else the golden);
+    `out` is the stream itself or None."""
+    if native.have_ref():
+        res, prop, out = ref_stream(c, data)
+        return dict(record(c, res, prop, out), out=out)
+    return dict((golden or load_golden())["by_key"][key(c)], out=None)
+
+
+def check_block(got, want, what):
+    """got = (res, dest_len, prop, bytes) of a block encode with ample room
+    against expect()'s record: the reference's stream minus its last byte."""
+    res, dl, prop, out = got
+    assert res == want["res"], (what, res, want["res"])
+    if res != OK:
+        assert dl == 0 and out == b"", what
+        return
+    assert prop == want["prop"], (what, prop, want["prop"])
+    assert dl == len(out) == want["len"] - 1, (what, dl, want["len"])
+    full = out + b"\0"
+    assert [list(t) for t in parse_chunks(full)] == want["chunks"], what
+    if want["out"] is not None:
+        assert full == want["out"], what
+    else:
+        assert full[:32].hex() == want["head"] and sha(full) == want["sha256"], what
+
+
+# ---------------------------------------------------------------- the emulator
+
+class CLzmaEncProps(ctypes.Structure):
+    _fields_ = [("level", ctypes.c_int), ("dictSize", ctypes.c_uint32), ("lc", ctypes.c_int),
+                ("lp", ctypes.c_int), ("pb", ctypes.c_int), ("algo", ctypes.c_int),
+                ("fb", ctypes.c_int), ("btMode", ctypes.c_int), ("numHashBytes", ctypes.c_int),
+                ("mc", ctypes.c_uint32), ("writeEndMark", ctypes.c_uint),
+                ("numThreads", ctypes.c_int)]
+
+
+class CLzma2EncProps(ctypes.Structure):
+    _fields_ = [("lzmaProps", CLzmaEncProps), ("blockSize", ctypes.c_size_t),
+                ("numBlockThreads", ctypes.c_int), ("numTotalThreads", ctypes.c_int)]
+
+
+def build_emu(out_dir, extra=(), main=False, name=None):
+    out = os.path.join(str(out_dir), name or ("lzma2enc_emu_main" if main else "liblzma2enc_emu.so"))
+    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-I", CSRC]
+    cmd += (["-DLZMA2ENC_EMU_MAIN"] if main else ["-fPIC", "-shared"])
+    cmd += list(extra) if extra else ["-O2"]
+    subprocess.run(cmd + [EMU_SRC, "-o", out], check=True)
+    return out
+
+
+def load_emu(so):
+    lib = ctypes.CDLL(so)
+    f = lib.lzma2enc_emu_encode
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int,
+                  ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                  ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_uint64)]
+    lib.lzma2enc_emu_slice_bytes.restype = None
+    lib.lzma2enc_emu_slice_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    for name in ("lzma2enc_emu_props_init", "lzma2enc_emu_props_normalize"):
+        g = getattr(lib, name)
+        g.restype = None
+        g.argtypes = [ctypes.POINTER(CLzma2EncProps)]
+    lib.lzma2enc_emu_prop_byte.restype = ctypes.c_int
+    lib.lzma2enc_emu_prop_byte.argtypes = [ctypes.c_uint32]
+    return lib
+
+
+def emu_encode(lib, data, c, cap, poison=0x3C):
+    """(res, dest_len, prop, dst[:dest_len]); asserts the guard behind cap."""
+    dst = ctypes.create_string_buffer(b"\xEE" * (cap + 8), cap + 8)
+    prop = ctypes.c_ubyte(0)
+    dl = ctypes.c_uint64(0)
+    res = lib.lzma2enc_emu_encode(data, len(data), dst, cap, c["level"], c["dict"], c["lc"],
+                                  c["lp"], c["pb"], poison, ctypes.byref(prop), ctypes.byref(dl))
+    assert dst.raw[cap:] == b"\xEE" * 8, "write past dst_cap"
+    assert dl.value <= cap
+    return res, dl.value, prop.value, dst.raw[:dl.value]
+
+
+def write_case_file(path, cases, golden=None):
+    """Records for the stand-alone build of lzma2enc_emu.cpp (sanitizer runs),
+    each with dst_cap = the block bound.  Expected bytes come from the live
+    reference where built, else from the library build of the emulator, which
+    the golden test pins."""
+    lib = None
+    with open(path, "wb") as f:
+        for c in cases:
+            data = data_of(c)
+            want = expect(c, data, golden)
+            cap = block_bound(len(data))
+            out = want["out"]
+            if want["res"] != OK:
+                out = b""
+            elif out is None:
+                if lib is None:
+                    lib = load_emu(build_emu(os.path.dirname(path), name="liblzma2enc_emu_dump.so"))
+                got = emu_encode(lib, data, c, cap)
+                check_block(got, want, key(c))
+                out = got[3]
+            else:
+                out = out[:-1]
+            f.write(struct.pack("<iIiii", c["level"], c["dict"], c["lc"], c["lp"], c["pb"]))
+            f.write(struct.pack("<QQiQ", len(data), cap, want["res"], len(out)))
+            f.write(data + out)
