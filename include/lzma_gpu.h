@@ -822,6 +822,63 @@ SRes Ppmd7Gpu_DecodeBatchHost(const Ppmd7GpuStreamDesc *descs, size_t n, const B
                               size_t src_size, Byte *dst, size_t dst_size,
                               Ppmd7GpuResult *results, uint64_t workspace_limit);
 
+/* Ppmd7.c + Ppmd7Enc.c on the GPU: the same model behind the reference's 7z
+ * range encoder, Ppmd7z_RangeEnc_Init, Ppmd7_EncodeSymbol for each of src_len
+ * bytes and Ppmd7z_RangeEnc_FlushData, bit for bit the reference's stream.  No
+ * end mark is written (7z streams carry none); src_len == 0 gives the five
+ * zero bytes of the flush.  Per stream, checked in this order:
+ *   order outside 2..64 or mem_size outside 1<<11 .. 0xFFFFFFFF-36
+ *                        SZ_ERROR_PARAM, dest_len = packed_len = 0, nothing
+ *                        read or written
+ *   stream longer than dst_cap
+ *                        SZ_ERROR_OUTPUT_EOF, dest_len == dst_cap, dst holds
+ *                        the first dst_cap bytes of the stream and packed_len
+ *                        its whole length (the encode runs to the end, so a
+ *                        caller can retry with that capacity)
+ *   else                 SZ_OK, dest_len == packed_len
+ * (SZ_ERROR_FAIL, the stream stopping where it is, if a suffix chain of the
+ * model ends without the symbol: the root context holds all 256 bytes, so
+ * this does not happen with a slice that nothing else writes.)
+ * Bytes of d_dst outside [dst_off, dst_off + dest_len) are never written.
+ * PPMd7 has no tight output bound: incompressible input grows, e.g. 4,096
+ * random bytes pack to 4,405 at order 2.  Size dst_cap generously and retry
+ * the streams that report SZ_ERROR_OUTPUT_EOF with their packed_len. */
+typedef struct Ppmd7GpuEncDesc {   /* 48 bytes */
+  uint64_t src_off;   /* plain bytes start in d_src */
+  uint64_t src_len;   /* plain bytes */
+  uint64_t dst_off;   /* packed range start in d_dst */
+  uint64_t dst_cap;   /* packed range capacity */
+  uint64_t ws_off;    /* slice, Ppmd7Gpu_WorkspaceBytes(mem_size), multiple of 256 */
+  uint32_t mem_size;
+  uint32_t order;
+} Ppmd7GpuEncDesc;
+
+typedef struct Ppmd7GpuEncResult { /* 24 bytes */
+  int32_t res;
+  uint32_t _pad;
+  uint64_t dest_len;    /* bytes written, <= dst_cap */
+  uint64_t packed_len;  /* length of the whole stream */
+} Ppmd7GpuEncResult;
+
+/* Encode n streams on the current device, one workgroup of one wave each, in
+ * index order (put long streams first); slices as for decoding.  All pointers
+ * are device memory owned by the caller; asynchronous on `stream`; n == 0 is a
+ * no-op.  Returns SZ_OK if the launch was queued (SZ_ERROR_FAIL without a
+ * device, SZ_ERROR_PARAM for n above 2^31 - 1); per-stream outcomes land in
+ * d_results. */
+SRes Ppmd7Gpu_EncodeBatch(const Ppmd7GpuEncDesc *d_descs, size_t n, const Byte *d_src, Byte *d_dst,
+                          void *d_workspace, Ppmd7GpuEncResult *d_results, void *stream);
+/* The same over host buffers: stages src and dst, lays the slices out itself
+ * (descs[i].ws_off is ignored), orders the streams longest src_len first and
+ * encodes in as many launches as keep the workspace at or under
+ * workspace_limit bytes (0 = half of the device's free memory).  SZ_ERROR_MEM
+ * if one stream's slice alone exceeds the limit or an allocation fails,
+ * SZ_ERROR_PARAM for a range outside src / dst, SZ_ERROR_FAIL without a
+ * device. */
+SRes Ppmd7Gpu_EncodeBatchHost(const Ppmd7GpuEncDesc *descs, size_t n, const Byte *src, size_t src_size,
+                              Byte *dst, size_t dst_size, Ppmd7GpuEncResult *results,
+                              uint64_t workspace_limit);
+
 /* ---------------------------------------------------------------- LZMA fast-mode encoding */
 
 /* The reference's encoder for props that normalise to algo == 0 and

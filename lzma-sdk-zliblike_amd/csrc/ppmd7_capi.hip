@@ -1,4 +1,4 @@
-// ppmd7_capi.hip -- C ABI of the PPMd7 batch decoder (include/lzma_gpu.h).
+// ppmd7_capi.hip -- C ABI of the PPMd7 batch decoder and encoder (include/lzma_gpu.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,16 +34,34 @@ extern "C" SRes Ppmd7Gpu_DecodeBatch(const Ppmd7GpuStreamDesc* d_descs, size_t n
   return SZ_OK;
 }
 
-static SRes decode_batch_host(const Ppmd7GpuStreamDesc* descs, size_t n, const Byte* src,
-                              size_t src_size, Byte* dst, size_t dst_size,
-                              Ppmd7GpuResult* results, uint64_t workspace_limit) {
+extern "C" SRes Ppmd7Gpu_EncodeBatch(const Ppmd7GpuEncDesc* d_descs, size_t n, const Byte* d_src,
+                                     Byte* d_dst, void* d_workspace,
+                                     Ppmd7GpuEncResult* d_results, void* stream) {
+  if (!ensure_device()) return SZ_ERROR_FAIL;
+  if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
+  if (n == 0) return SZ_OK;
+  if (ppmd7encgpu_launch(d_descs, uint32_t(n), d_src, d_dst, static_cast<uint8_t*>(d_workspace),
+                         d_results, static_cast<hipStream_t>(stream)) != 0) {
+    set_error("PPMd7 batch kernel launch failed");
+    return SZ_ERROR_FAIL;
+  }
+  return SZ_OK;
+}
+
+// The host call of either direction.  Desc is Ppmd7GpuStreamDesc or
+// Ppmd7GpuEncDesc (one layout); dst_bytes(d) is the stream's range in dst,
+// work(d) what its run time grows with, launch the direction's kernel launcher.
+template <class Desc, class Res, class DstBytes, class Work, class Launch>
+static SRes batch_host(const Desc* descs, size_t n, const Byte* src, size_t src_size, Byte* dst,
+                       size_t dst_size, Res* results, uint64_t workspace_limit,
+                       DstBytes dst_bytes, Work work, Launch launch) {
   if (!ensure_device()) return SZ_ERROR_FAIL;
   if (n == 0) return SZ_OK;
   if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
   for (size_t i = 0; i < n; ++i) {
-    const Ppmd7GpuStreamDesc& d = descs[i];
+    const Desc& d = descs[i];
     if (d.src_off > src_size || d.src_len > src_size - d.src_off || d.dst_off > dst_size ||
-        d.dst_len > dst_size - d.dst_off)
+        dst_bytes(d) > dst_size - d.dst_off)
       return SZ_ERROR_PARAM;
   }
   if (workspace_limit == 0) {
@@ -55,9 +73,9 @@ static SRes decode_batch_host(const Ppmd7GpuStreamDesc* descs, size_t n, const B
   std::vector<uint32_t> order(n);
   std::iota(order.begin(), order.end(), 0u);
   std::stable_sort(order.begin(), order.end(),
-                   [&](uint32_t a, uint32_t b) { return descs[a].dst_len > descs[b].dst_len; });
+                   [&](uint32_t a, uint32_t b) { return work(descs[a]) > work(descs[b]); });
   // launches: consecutive streams of the order while their slices fit the limit
-  std::vector<Ppmd7GpuStreamDesc> d(n);
+  std::vector<Desc> d(n);
   std::vector<size_t> cut{0};
   uint64_t ws_max = 0, ws_cur = 0;
   for (size_t k = 0; k < n; ++k) {
@@ -78,8 +96,8 @@ static SRes decode_batch_host(const Ppmd7GpuStreamDesc* descs, size_t n, const B
   cut.push_back(n);
 
   DevArr<uint8_t> g_src, g_dst, g_ws;
-  DevArr<Ppmd7GpuStreamDesc> g_desc;
-  DevArr<Ppmd7GpuResult> g_res;
+  DevArr<Desc> g_desc;
+  DevArr<Res> g_res;
   if (!g_src.alloc(src_size) || !g_dst.alloc(dst_size) || !g_ws.alloc(ws_max) ||
       !g_desc.alloc(n) || !g_res.alloc(n)) {
     (void)hipGetLastError();
@@ -94,13 +112,12 @@ static SRes decode_batch_host(const Ppmd7GpuStreamDesc* descs, size_t n, const B
   for (size_t c = 0; c + 1 < cut.size(); ++c) {
     const size_t lo = cut[c], cnt = cut[c + 1] - lo;
     if (cnt == 0) continue;
-    if (ppmd7gpu_launch(g_desc.p + lo, uint32_t(cnt), g_src.p, g_dst.p, g_ws.p, g_res.p + lo,
-                        nullptr) != 0) {
+    if (launch(g_desc.p + lo, uint32_t(cnt), g_src.p, g_dst.p, g_ws.p, g_res.p + lo, nullptr) != 0) {
       set_error("PPMd7 batch kernel launch failed");
       return SZ_ERROR_FAIL;
     }
   }
-  std::vector<Ppmd7GpuResult> r(n);
+  std::vector<Res> r(n);
   if (!hip_ok(hipDeviceSynchronize(), "PPMd7 batch") ||
       !hip_ok(hipMemcpy(r.data(), g_res.p, n * sizeof(r[0]), hipMemcpyDeviceToHost),
               "download results") ||
@@ -114,7 +131,23 @@ extern "C" SRes Ppmd7Gpu_DecodeBatchHost(const Ppmd7GpuStreamDesc* descs, size_t
                                          size_t src_size, Byte* dst, size_t dst_size,
                                          Ppmd7GpuResult* results, uint64_t workspace_limit) {
   try {
-    return decode_batch_host(descs, n, src, src_size, dst, dst_size, results, workspace_limit);
+    const auto len = [](const Ppmd7GpuStreamDesc& d) { return d.dst_len; };
+    return batch_host(descs, n, src, src_size, dst, dst_size, results, workspace_limit, len, len,
+                      ppmd7gpu_launch);
+  } catch (const std::exception&) {
+    set_error("PPMd7 batch: host allocation failed");
+    return SZ_ERROR_MEM;
+  }
+}
+
+extern "C" SRes Ppmd7Gpu_EncodeBatchHost(const Ppmd7GpuEncDesc* descs, size_t n, const Byte* src,
+                                         size_t src_size, Byte* dst, size_t dst_size,
+                                         Ppmd7GpuEncResult* results, uint64_t workspace_limit) {
+  try {
+    return batch_host(
+        descs, n, src, src_size, dst, dst_size, results, workspace_limit,
+        [](const Ppmd7GpuEncDesc& d) { return d.dst_cap; },
+        [](const Ppmd7GpuEncDesc& d) { return d.src_len; }, ppmd7encgpu_launch);
   } catch (const std::exception&) {
     set_error("PPMd7 batch: host allocation failed");
     return SZ_ERROR_MEM;

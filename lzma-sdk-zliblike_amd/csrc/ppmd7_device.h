@@ -3,7 +3,9 @@
 // meant to live in registers.  A restatement of what Ppmd7.c / Ppmd7Dec.c and
 // SzDecodePpmd (7zDec.c:66-122) compute; every decision of the allocator is the
 // reference's, because the model restarts when memory runs out and the decoded
-// bytes therefore depend on which allocation fails.
+// bytes therefore depend on which allocation fails.  The encoder (Ppmd7Enc.c:
+// struct Ppmd7Enc at the end) derives from it and shares everything after the
+// choice of a state, update_found().
 //
 // Memory: the model is a byte array of `align_off + mem_size + 12` bytes
 // (ppmd7_model_bytes) addressed by 32-bit offsets, 0 meaning "none" -- the
@@ -22,7 +24,8 @@
 // Lanes: on the device all lanes of the wave run this code on the same state
 // (wave-uniform control flow, identical stores to identical addresses).  The
 // bulk initialisations are dealt over the lanes (lane, nlanes) and followed by
-// PPMD7_SYNC(); the host build is lane 0 of 1.
+// PPMD7_SYNC(), and so are the encoder's searches for its symbol
+// (Ppmd7Enc::scan_states); the host build is lane 0 of 1.
 //
 // The input never steers an address: the range decoder only picks which of the
 // model's own, consistent transitions is taken, so every offset stays inside
@@ -577,6 +580,66 @@ struct Ppmd7 {
     return cell;
   }
 
+  // BinSumm cell of the one-state context whose state is s (Ppmd7_GetBinSumm);
+  // sets hi_flag as the reference's macro does
+  PPMD7_FN uint32_t bin_cell(uint32_t s) {
+    const uint32_t f = s_freq(s);
+    hi_flag = high_flag(s_sym(found));
+    const uint32_t up = c_n(c_suffix(min_ctx)) - 1;
+    const uint32_t by_up = up == 0 ? 0u : up == 1 ? 2u : up < 11 ? 4u : 6u;
+    return (((f - 1) << 6) + prev_success + by_up + hi_flag + 2 * high_flag(s_sym(s)) +
+            ((uint32_t(run_len >> 26)) & 0x20u)) &
+           (kPpmd7BinCells - 1);
+  }
+
+  // how `found` was reached in min_ctx
+  enum How : uint32_t { kFirst, kOther, kBinary, kEscaped };
+
+  // Everything after the state is chosen, for both directions: Ppmd7_Update1_0
+  // / Update1 / UpdateBin / Update2 with Rescale, then NextContext's successor
+  // shortcut or UpdateModel, and the restart when memory ran out.
+  PPMD7_FN void update_found(How how) {
+    bool need_rescale = false;
+    if (how == kBinary) {
+      const uint32_t f = s_freq(found);
+      w8(found + 1, f + (f < 128 ? 1 : 0));
+      prev_success = 1;
+      ++run_len;
+    } else {
+      uint32_t f = s_freq(found);
+      const uint32_t sum = c_sum(min_ctx);
+      if (how == kFirst) {
+        prev_success = 2 * f > sum ? 1u : 0u;
+        run_len += int32_t(prev_success);
+      }
+      f = (f + 4) & 0xFFu;
+      w8(found + 1, f);
+      w16(min_ctx + 2, sum + 4);
+      if (how == kOther) {
+        if (f > s_freq(found - 6)) {
+          s_swap(found, found - 6);
+          found -= 6;
+          need_rescale = f > kPpmd7MaxFreq;
+        }
+      } else {
+        need_rescale = f > kPpmd7MaxFreq;
+      }
+    }
+    if (need_rescale) rescale();
+    bool follow = false;
+    uint32_t next = 0;
+    if (how == kEscaped) {
+      run_len = init_rl;
+    } else if (order_fall == 0) {
+      next = s_succ(found);
+      follow = next > text;
+    }
+    if (follow)
+      min_ctx = max_ctx = next;
+    else if (!update_model())
+      restart_model();
+  }
+
   // ---------------------------------------------------------------- range decoder
   PPMD7_FN uint32_t read_byte() {
     if (pos < len) return src[pos++];
@@ -620,7 +683,7 @@ struct Ppmd7 {
   // one symbol: 0..255, -1 end of the suffix chain, -2 a count outside the
   // model's total
   PPMD7_FN int decode_symbol() {
-    enum { kFirst, kOther, kBinary, kEscaped } how = kEscaped;
+    How how = kEscaped;
     const uint32_t ns0 = c_n(min_ctx);
     bool escaped = false;
     if (ns0 != 1) {
@@ -661,13 +724,7 @@ struct Ppmd7 {
       }
     } else {
       const uint32_t s = min_ctx + 2;
-      const uint32_t f = s_freq(s);
-      hi_flag = high_flag(s_sym(found));
-      const uint32_t up = c_n(c_suffix(min_ctx)) - 1;
-      const uint32_t by_up = up == 0 ? 0u : up == 1 ? 2u : up < 11 ? 4u : 6u;
-      const uint32_t cell = (((f - 1) << 6) + prev_success + by_up + hi_flag +
-                             2 * high_flag(s_sym(s)) + ((uint32_t(run_len >> 26)) & 0x20u)) &
-                            (kPpmd7BinCells - 1);
+      const uint32_t cell = bin_cell(s);
       const uint32_t pr = bin[cell];
       const uint32_t bound = (range >> 14) * pr;
       if (code < bound) {
@@ -735,45 +792,7 @@ struct Ppmd7 {
     }
 
     const uint32_t symbol = s_sym(found);
-    bool need_rescale = false;
-    if (how == kBinary) {
-      const uint32_t f = s_freq(found);
-      w8(found + 1, f + (f < 128 ? 1 : 0));
-      prev_success = 1;
-      ++run_len;
-    } else {
-      uint32_t f = s_freq(found);
-      const uint32_t sum = c_sum(min_ctx);
-      if (how == kFirst) {
-        prev_success = 2 * f > sum ? 1u : 0u;
-        run_len += int32_t(prev_success);
-      }
-      f = (f + 4) & 0xFFu;
-      w8(found + 1, f);
-      w16(min_ctx + 2, sum + 4);
-      if (how == kOther) {
-        if (f > s_freq(found - 6)) {
-          s_swap(found, found - 6);
-          found -= 6;
-          need_rescale = f > kPpmd7MaxFreq;
-        }
-      } else {
-        need_rescale = f > kPpmd7MaxFreq;
-      }
-    }
-    if (need_rescale) rescale();
-    bool follow = false;
-    uint32_t next = 0;
-    if (how == kEscaped) {
-      run_len = init_rl;
-    } else if (order_fall == 0) {
-      next = s_succ(found);
-      follow = next > text;
-    }
-    if (follow)
-      min_ctx = max_ctx = next;
-    else if (!update_model())
-      restart_model();
+    update_found(how);
     return int(symbol);
   }
 };
@@ -816,5 +835,251 @@ PPMD7_TOP Ppmd7Out ppmd7_decode_stream(const uint8_t* src, uint64_t src_len, uin
   }
   out.dest_len = i;
   out.src_len = p.pos;
+  return out;
+}
+
+// ---------------------------------------------------------------- encoder
+// Ppmd7Enc.c on the same model: the 7z range encoder (Ppmd7Enc.c:9-72) and
+// Ppmd7_EncodeSymbol (Ppmd7Enc.c:77-185).  The symbol only selects which state
+// of the model's own contexts is taken, so, as in the decoder, no input byte
+// steers an address.  The output position counts every byte of the stream;
+// a byte is stored only while the position is below dst_cap.
+#ifndef PPMD7_ENC_COUNT
+#define PPMD7_ENC_COUNT(carry, pending) ((void)0)  // the host build counts carries here
+#endif
+
+struct Ppmd7EncOut {
+  int32_t res;
+  uint64_t dest_len, packed_len;
+};
+
+struct Ppmd7Enc : Ppmd7 {
+  uint64_t low, cache_size;  // range is Ppmd7::range
+  uint32_t cache;
+  uint8_t* dst;
+  uint64_t out_pos, dst_cap;
+
+  PPMD7_FN void rc_enc_init() {
+    low = 0;
+    range = 0xFFFFFFFFu;
+    cache = 0;
+    cache_size = 1;
+    out_pos = 0;
+  }
+  PPMD7_FN void put_byte(uint32_t b) {
+    if (out_pos < dst_cap) dst[out_pos] = uint8_t(b);
+    ++out_pos;
+  }
+  // RangeEnc_ShiftLow: the byte held back and the 0xFF bytes pending behind it
+  // go out once a carry into them is decided
+  PPMD7_FN void shift_low() {
+    const uint32_t carry = uint32_t(low >> 32);
+    if (uint32_t(low) < 0xFF000000u || carry != 0) {
+      PPMD7_ENC_COUNT(carry, cache_size);
+      uint32_t b = cache;
+      do {
+        put_byte((b + carry) & 0xFFu);
+        b = 0xFF;
+      } while (--cache_size != 0);
+      cache = uint32_t(low) >> 24;
+    }
+    ++cache_size;
+    low = uint64_t(uint32_t(low) << 8);
+  }
+  PPMD7_FN void rc_enc_normalize() {
+    while (range < kPpmd7RcTop) {
+      range <<= 8;
+      shift_low();
+    }
+  }
+  PPMD7_FN void rc_encode(uint32_t start, uint32_t width, uint32_t total) {
+    range /= total;
+    low += uint32_t(start * range);
+    range *= width;
+    rc_enc_normalize();
+  }
+  PPMD7_FN void rc_enc_flush() {
+    for (int i = 0; i < 5; ++i) shift_low();
+  }
+
+  // The encoder knows its symbol, so a context's states are searched by all
+  // lanes at once, lane l taking state l, l + nlanes, ...  Returns the
+  // symbol's index among the ns states at `stats` (ns: absent) with `before`
+  // the frequency sum in front of it (absent: of all).  kMasked: frequencies
+  // count through the exclusion mask, every state's symbol is excluded as it
+  // is passed and `whole` is the sum over all states; else the scan stops at
+  // the hit.  Lane 0 of 1 runs this as the serial loop.
+#ifdef PPMD7_HOST_EMU
+  PPMD7_FN static uint64_t wave_ballot(bool p) { return p ? 1u : 0u; }
+  PPMD7_FN static uint32_t wave_add(uint32_t v) { return v; }
+#else
+  PPMD7_FN static uint64_t wave_ballot(bool p) { return __ballot(p); }
+  PPMD7_FN static uint32_t wave_add(uint32_t v) {
+    for (int d = 32; d != 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+  }
+#endif
+  template <bool kMasked>
+  PPMD7_FN uint32_t scan_states(uint32_t stats, uint32_t ns, uint32_t sym, uint32_t& before,
+                                uint32_t& whole) {
+    uint32_t hit = ns;
+    before = whole = 0;
+    for (uint32_t base = 0; base < ns; base += nlanes) {
+      const uint32_t i = base + lane;
+      const bool in = i < ns;
+      const uint32_t w = in ? r16(stats + 6 * i) : 0u;  // symbol | frequency << 8
+      const uint32_t cur = w & 0xFFu;
+      uint32_t f = w >> 8;
+      if (kMasked && in) {
+        f &= h->mask[cur];
+        h->mask[cur] = 0;
+      }
+      // one wave sum for both: a chunk's frequencies stay below 1 << 16
+      uint32_t part = f << 16;
+      if (hit == ns) {
+        const uint64_t m = wave_ballot(in && cur == sym);
+        if (m != 0) {
+          const uint32_t pos = uint32_t(__builtin_ctzll(m));
+          hit = base + pos;
+          part |= lane < pos ? f : 0u;
+        } else {
+          part |= f;
+        }
+      }
+      const uint32_t r = wave_add(part);
+      before += r & 0xFFFFu;
+      whole += r >> 16;
+      if (!kMasked && hit != ns) break;
+    }
+    if (kMasked) PPMD7_SYNC();
+    return hit;
+  }
+
+  // false: the suffix chain ended without the symbol (the reference's end-mark
+  // return; the root context holds every byte, so no byte symbol gets here
+  // with a consistent model)
+  PPMD7_FN bool encode_symbol(uint32_t sym) {
+    How how = kEscaped;
+    const uint32_t ns0 = c_n(min_ctx);
+    bool escaped = false;
+    if (ns0 != 1) {
+      const uint32_t stats = c_states(min_ctx), total = c_sum(min_ctx);
+      uint32_t before, whole;
+      const uint32_t at = scan_states<false>(stats, ns0, sym, before, whole);
+      if (at == 0) {
+        rc_encode(0, s_freq(stats), total);
+        found = stats;
+        how = kFirst;
+      } else {
+        prev_success = 0;
+        if (at != ns0) {
+          const uint32_t s = stats + 6 * at;
+          rc_encode(before, s_freq(s), total);
+          found = s;
+          how = kOther;
+        } else {
+          hi_flag = high_flag(s_sym(found));
+          mask_all();
+          for (uint32_t i = lane; i < ns0; i += nlanes) h->mask[s_sym(stats + 6 * i)] = 0;
+          PPMD7_SYNC();
+          rc_encode(before, total - before, total);
+          escaped = true;
+        }
+      }
+    } else {
+      const uint32_t s = min_ctx + 2;
+      const uint32_t cell = bin_cell(s);
+      const uint32_t pr = bin[cell];
+      const uint32_t bound = (range >> 14) * pr;
+      if (s_sym(s) == sym) {
+        range = bound;
+        rc_enc_normalize();
+        bin[cell] = uint16_t(pr + 128 - ((pr + 32) >> 7));
+        found = s;
+        how = kBinary;
+      } else {
+        low += bound;
+        range -= bound;
+        rc_enc_normalize();
+        const uint32_t np = pr - ((pr + 32) >> 7);
+        bin[cell] = uint16_t(np);
+        init_esc = h->esc_start[(np >> 10) & 15u];
+        mask_all();
+        h->mask[s_sym(s)] = 0;
+        prev_success = 0;
+        escaped = true;
+      }
+    }
+
+    while (escaped) {
+      const uint32_t masked = c_n(min_ctx);
+      do {
+        ++order_fall;
+        const uint32_t up = c_suffix(min_ctx);
+        if (up == 0) return false;
+        min_ctx = up;
+      } while (c_n(min_ctx) == masked);
+      uint32_t esc;
+      const uint32_t cell = escape_estimate(masked, esc);
+      uint32_t before, sum;
+      const uint32_t ns = c_n(min_ctx), stats = c_states(min_ctx);
+      const uint32_t at = scan_states<true>(stats, ns, sym, before, sum);
+      const uint32_t hit = at != ns ? stats + 6 * at : 0u;
+      const uint32_t total = sum + esc;
+      if (hit != 0) {
+        rc_encode(before, s_freq(hit), total);
+        Ppmd7See v = h->see[cell];
+        if (v.shift < 7 && --v.count == 0) {
+          v.summ = uint16_t(v.summ << 1);
+          v.count = uint8_t(3u << v.shift++);
+        }
+        h->see[cell] = v;
+        found = hit;
+        break;
+      }
+      rc_encode(sum, esc, total);
+      h->see[cell].summ = uint16_t(h->see[cell].summ + total);
+    }
+    update_found(how);
+    return true;
+  }
+};
+
+// Ppmd7z_RangeEnc_Init, Ppmd7_EncodeSymbol over src_len bytes and
+// Ppmd7z_RangeEnc_FlushData, with no end mark (7z streams carry none).  `hot`,
+// `bin` and `model` as for ppmd7_decode_stream.  res: 0; 5 (SZ_ERROR_PARAM) for
+// order / mem_size out of range, nothing read or written; 7
+// (SZ_ERROR_OUTPUT_EOF) when the stream is longer than dst_cap -- dst then
+// holds its first dst_cap bytes and packed_len its whole length; 11
+// (SZ_ERROR_FAIL) if a suffix chain ended without the symbol, the stream
+// stopping there.
+PPMD7_TOP Ppmd7EncOut ppmd7_encode_stream(const uint8_t* src, uint64_t src_len, uint8_t* dst,
+                                         uint64_t dst_cap, uint32_t order, uint32_t mem_size,
+                                         uint8_t* model, Ppmd7Hot* hot, uint16_t* bin,
+                                         uint32_t lane, uint32_t nlanes) {
+  Ppmd7EncOut out;
+  out.dest_len = 0;
+  out.packed_len = 0;
+  if (order < kPpmd7MinOrder || order > kPpmd7MaxOrder || mem_size < kPpmd7MinMem ||
+      mem_size > kPpmd7MaxMem) {
+    out.res = 5;  // SZ_ERROR_PARAM
+    return out;
+  }
+  Ppmd7Enc p;
+  p.m = model;
+  p.h = hot;
+  p.bin = bin;
+  p.lane = lane;
+  p.nlanes = nlanes;
+  p.dst = dst;
+  p.dst_cap = dst_cap;
+  p.rc_enc_init();
+  if (src_len != 0) p.init_model(order, mem_size);
+  bool ok = true;
+  for (uint64_t i = 0; i < src_len && ok; ++i) ok = p.encode_symbol(src[i]);
+  if (ok) p.rc_enc_flush();
+  out.packed_len = p.out_pos;
+  out.dest_len = p.out_pos < dst_cap ? p.out_pos : dst_cap;
+  out.res = !ok ? 11 : p.out_pos > dst_cap ? 7 : 0;
   return out;
 }

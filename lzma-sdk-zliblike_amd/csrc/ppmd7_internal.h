@@ -1,5 +1,5 @@
 // ppmd7_internal.h -- the PPMd7 workspace slice layout and launcher, shared by
-// ppmd7_kernels.hip, ppmd7_capi.hip and sevenz_capi.hip.
+// ppmd7_kernels.hip, ppmd7enc_kernels.hip, ppmd7_capi.hip and sevenz_capi.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,3 +22,7 @@ __host__ __device__ inline uint64_t ppmd7_slice_bytes(uint32_t mem_size) {
 extern "C" int ppmd7gpu_launch(const Ppmd7GpuStreamDesc* d_descs, uint32_t n, const uint8_t* d_src,
                                uint8_t* d_dst, uint8_t* d_ws, Ppmd7GpuResult* d_results,
                                hipStream_t stream);
+// the encoder (ppmd7enc_kernels.hip): the same shape and slices
+extern "C" int ppmd7encgpu_launch(const Ppmd7GpuEncDesc* d_descs, uint32_t n, const uint8_t* d_src,
+                                  uint8_t* d_dst, uint8_t* d_ws, Ppmd7GpuEncResult* d_results,
+                                  hipStream_t stream);

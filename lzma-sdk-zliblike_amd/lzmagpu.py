@@ -187,6 +187,20 @@ class Ppmd7Result(ctypes.Structure):
                 ("src_len", ctypes.c_uint64)]
 
 
+class Ppmd7EncDesc(ctypes.Structure):
+    """Ppmd7GpuEncDesc (include/lzma_gpu.h): one plain buffer of an encode batch."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("src_len", ctypes.c_uint64),
+                ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64),
+                ("ws_off", ctypes.c_uint64), ("mem_size", ctypes.c_uint32),
+                ("order", ctypes.c_uint32)]
+
+
+class Ppmd7EncResult(ctypes.Structure):
+    """Ppmd7GpuEncResult: res, bytes written, length of the whole stream."""
+    _fields_ = [("res", ctypes.c_int32), ("_pad", ctypes.c_uint32), ("dest_len", ctypes.c_uint64),
+                ("packed_len", ctypes.c_uint64)]
+
+
 class CLzmaEncProps(ctypes.Structure):
     """CLzmaEncProps (LzmaEnc.h:15-31)."""
     _fields_ = [("level", ctypes.c_int), ("dictSize", ctypes.c_uint32), ("lc", ctypes.c_int),
@@ -263,6 +277,7 @@ assert ctypes.sizeof(PlanOptions) == 40
 assert ctypes.sizeof(CLzmaDec) == 136
 assert ctypes.sizeof(CSha256) == 104
 assert ctypes.sizeof(Ppmd7StreamDesc) == 48 and ctypes.sizeof(Ppmd7Result) == 24
+assert ctypes.sizeof(Ppmd7EncDesc) == 48 and ctypes.sizeof(Ppmd7EncResult) == 24
 assert ctypes.sizeof(CLzmaEncProps) == 48
 assert ctypes.sizeof(EncStreamDesc) == 72 and ctypes.sizeof(EncResult) == 16
 
@@ -346,6 +361,10 @@ _sig = {
     "Ppmd7Gpu_DecodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Ppmd7StreamDesc), ctypes.c_size_t, _P,
                                                 ctypes.c_size_t, _P, ctypes.c_size_t,
                                                 ctypes.POINTER(Ppmd7Result), ctypes.c_uint64]),
+    "Ppmd7Gpu_EncodeBatch": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "Ppmd7Gpu_EncodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Ppmd7EncDesc), ctypes.c_size_t, _P,
+                                                ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                ctypes.POINTER(Ppmd7EncResult), ctypes.c_uint64]),
     "LzmaEncProps_Init": (None, [ctypes.POINTER(CLzmaEncProps)]),
     "LzmaEncProps_Normalize": (None, [ctypes.POINTER(CLzmaEncProps)]),
     "LzmaEncProps_GetDictSize": (ctypes.c_uint32, [ctypes.POINTER(CLzmaEncProps)]),
@@ -946,6 +965,34 @@ def ppmd7_decode_batch_host(descs, n, src, dst, workspace_limit=0):
     res = (Ppmd7Result * max(n, 1))()
     d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
     r = _lib.Ppmd7Gpu_DecodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
+                                      workspace_limit)
+    return r, res, d.raw[:len(dst)]
+
+
+def ppmd7_make_enc_descs(items):
+    """items: dicts with src_off, src_len, dst_off, dst_cap, order, mem_size and
+    optionally ws_off.  Returns a ctypes Ppmd7EncDesc array."""
+    arr = (Ppmd7EncDesc * max(len(items), 1))()
+    for i, it in enumerate(items):
+        d = arr[i]
+        d.src_off, d.src_len = it["src_off"], it["src_len"]
+        d.dst_off, d.dst_cap = it["dst_off"], it["dst_cap"]
+        d.ws_off = it.get("ws_off", 0)
+        d.mem_size, d.order = it["mem_size"], it["order"]
+    return arr
+
+
+def ppmd7_encode_batch_device(d_descs, n, d_src, d_dst, d_ws, d_results, stream=0):
+    """Ppmd7Gpu_EncodeBatch over raw device pointers (ints)."""
+    return _lib.Ppmd7Gpu_EncodeBatch(d_descs, n, d_src, d_dst, d_ws, d_results, stream or None)
+
+
+def ppmd7_encode_batch_host(descs, n, src, dst, workspace_limit=0):
+    """Ppmd7Gpu_EncodeBatchHost: dst (bytes) is the output buffer's initial
+    contents.  Returns (res, results[ctypes], dst bytes after the call)."""
+    res = (Ppmd7EncResult * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.Ppmd7Gpu_EncodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
                                       workspace_limit)
     return r, res, d.raw[:len(dst)]
 
