@@ -1175,6 +1175,188 @@ SRes LzmaGpu_7zOpenEx(const Byte *archive, size_t size, LzmaGpu7zFolder *folders
 SRes LzmaGpu_7zExtractEx(Byte *dest, SizeT *destLen, const Byte *archive, size_t size,
                          SRes *file_res, size_t file_cap, unsigned flags);
 
+/* ---- 7z archive writer: every folder of an archive in one encode batch ----
+ * The write side of the calls above.  The caller describes an archive as items
+ * over one source buffer; every folder (one item, or a JOIN group) is one
+ * stream of an LZMA, an LZMA2 (one stream per blockSize piece) or a PPMd7
+ * encode batch, all folders of the archive at once; CRC-32 of every file and
+ * the x86 / ARM filters run as batches over the uploaded source; the pack stage
+ * (SzGpu_PackBatch) gathers the finished pieces into the pack area on the
+ * device; the header is written on the host.  Format 7z 0.4 as the reference's
+ * reader accepts it (7zIn.c, CheckSupportedFolder 7zDec.c:269-322): one coder,
+ * or the main coder and a filter coder bound `in 1 <- out 0`, the filter at
+ * ip 0 over the folder's whole data before the main coder.  Pack streams: LZMA
+ * without end mark, LZMA2 in the multi-threaded layout with the final 0x00,
+ * PPMd7 without end mark (props: order, memSize LE32), Copy the bytes.  Every
+ * data file's CRC-32 is in SubStreamsInfo; no folder CRCs (except the packed
+ * header's); no times, no attributes: the archive is a function of its inputs.
+ * Not written: the optimal parser (levels 5+), BCJ2 folders, times and
+ * attributes, an archive that does not fit in device memory at once. */
+
+#define LZMA_GPU_7Z_ITEM_DIR 1u   /* a directory: size must be 0 */
+#define LZMA_GPU_7Z_ITEM_JOIN 2u  /* continues the folder of the previous data item (solid) */
+
+/* One archive entry.  size == 0 or DIR: no stream (kEmptyStream; kEmptyFile
+ * when not a directory), in the caller's position.  JOIN: the bytes continue
+ * the previous data item's folder: src_off must be where that item ended and
+ * method the same index, else SZ_ERROR_PARAM (JOIN on an entry without data
+ * means nothing). */
+typedef struct LzmaGpu7zItem {     /* 32 bytes */
+  uint64_t src_off, size;          /* range of the source buffer */
+  uint32_t name_off, name_len;     /* UTF-16 units into names; name_len counts the NUL */
+  uint32_t flags;                  /* LZMA_GPU_7Z_ITEM_* */
+  uint32_t method;                 /* index into the method table */
+} LzmaGpu7zItem;
+
+/* One row of the method table.  method: 0 Copy, 0x030101 LZMA (props.lzmaProps),
+ * 0x21 LZMA2 (props, blockSize after Lzma2EncProps_Normalize cuts the folder),
+ * 0x030401 PPMd7 (ppmd_order 2..64, ppmd_mem_size 1<<11 .. 0xFFFFFFFF-36);
+ * filter: 0 none, 4 x86, 7 ARM (the xz ids of BraGpu_Batch).  The props go
+ * through LzmaEncGpu_DescFromProps / Lzma2EncGpu_DescFromProps: their
+ * SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED (level 5 and up) stand. */
+typedef struct LzmaGpu7zMethod {   /* 88 bytes */
+  uint64_t method;
+  uint32_t filter;
+  uint32_t ppmd_order;
+  uint32_t ppmd_mem_size;
+  uint32_t reserved;               /* 0 */
+  CLzma2EncProps props;
+} LzmaGpu7zMethod;
+
+#define LZMA_GPU_7Z_WRITE_ENCODE_HEADER 1u
+#define LZMA_GPU_7Z_WRITE_TIMINGS 2u   /* synchronise after every stage and fill stats->stage_ns */
+#define LZMA_GPU_7Z_WRITE_KNOWN_FLAGS 3u
+typedef struct LzmaGpu7zWriteOptions {   /* 16 bytes */
+  uint32_t flags;
+  uint32_t reserved;               /* 0 */
+  uint64_t workspace_limit;        /* as in the *BatchHost calls; 0 = half of the free memory */
+} LzmaGpu7zWriteOptions;
+
+#define LZMA_GPU_7Z_STAGE_UPLOAD 0
+#define LZMA_GPU_7Z_STAGE_CRC 1
+#define LZMA_GPU_7Z_STAGE_FILTER 2
+#define LZMA_GPU_7Z_STAGE_ENCODE 3     /* the encode batches and the re-encode rounds */
+#define LZMA_GPU_7Z_STAGE_PACK 4
+#define LZMA_GPU_7Z_STAGE_DOWNLOAD 5   /* the pack area into dest */
+#define LZMA_GPU_7Z_STAGE_HEADER 6     /* the header on the host; with ENCODE_HEADER its LZMA stream */
+#define LZMA_GPU_7Z_STAGE_TOTAL 7      /* the call after the plan; set without TIMINGS too */
+typedef struct LzmaGpu7zWriteStats {     /* 112 bytes */
+  uint64_t folders;
+  uint64_t pieces;                 /* encode pieces and Copy ranges: the pack stage's input */
+  uint64_t reencoded;              /* streams encoded again with a larger slot */
+  uint64_t pack_bytes;             /* the pack area (with the packed header's stream) */
+  uint64_t header_bytes;           /* the header as it stands in the archive (the stub if packed) */
+  uint64_t encode_launches;        /* encode batch launches for the folders (1 per kind unless
+                                      workspace_limit cuts a batch or streams are re-encoded) */
+  uint64_t stage_ns[8];            /* LZMA_GPU_7Z_STAGE_*: host clock, nanoseconds */
+} LzmaGpu7zWriteStats;
+
+/* Host only, no device.  Checks the method table (in order; the first error is
+ * returned), then the items: SZ_ERROR_PARAM for an unknown method id or filter,
+ * PPMd props out of range, a flag bit outside DIR | JOIN, a DIR with size != 0,
+ * a method index, source range or name range out of bounds, a name_len of 0, a
+ * bad JOIN, more than 2^32 - 2 items; SZ_ERROR_UNSUPPORTED for an LZMA or PPMd7
+ * folder of 2^31 bytes or more.  Fills up to folder_cap folders (folders may be
+ * NULL): unpack_size, dst_off (the folder's start in the source), method, x86,
+ * num_coders (2 with a filter; x86 == 0 then means ARM), props / props_size,
+ * first_file (index of the folder's first item), num_files; pack_off, pack_size,
+ * crc_defined, crc are 0.  *n_pieces: encode pieces + Copy ranges.
+ * *dest_bound: a dest of that many bytes holds the archive whatever the data
+ * (slots, not streams, counted; with or without ENCODE_HEADER). */
+SRes LzmaGpu_7zWritePlan(const LzmaGpu7zItem *items, size_t n, size_t src_size, size_t names_len,
+                         const LzmaGpu7zMethod *methods, size_t n_methods,
+                         LzmaGpu7zFolder *folders, size_t folder_cap, size_t *n_folders,
+                         size_t *n_pieces, uint64_t *dest_bound);
+
+/* Host only.  flags 0: the header (kHeader, MainStreamsInfo, FilesInfo with
+ * kEmptyStream / kEmptyFile / kName) for `folders` (as the plan gives them, with
+ * pack_size set; pack streams back to back from pack_pos 0) and `items`;
+ * file_crcs[i] = CRC-32 of item i's bytes (read for data items only).
+ * LZMA_GPU_7Z_HEADER_STUB: the kEncodedHeader stub for folders[0] (n_folders 1:
+ * the folder that packs the header, at pack_off, with pack_size, unpack_size,
+ * props and its CRC when crc_defined); items are not read.
+ * *header_len is always set; SZ_ERROR_OUTPUT_EOF when header_cap is below it
+ * (header may be NULL).  sig32 (may be NULL): the 32-byte signature header for
+ * this header after a pack area of pack_area_size bytes. */
+#define LZMA_GPU_7Z_HEADER_STUB 1u
+SRes LzmaGpu_7zWriteHeader(const LzmaGpu7zFolder *folders, size_t n_folders,
+                           const LzmaGpu7zItem *items, size_t n, const uint32_t *file_crcs,
+                           const UInt16 *names, size_t names_len, unsigned flags, Byte *header,
+                           size_t header_cap, size_t *header_len, Byte *sig32,
+                           uint64_t pack_area_size);
+
+/* The whole archive from host memory: upload, CRC batch, filter batches (in
+ * place, after the CRCs; a filtered folder's source range may not overlap
+ * another folder's: SZ_ERROR_PARAM), the LZMA, LZMA2 and PPMd7 batches (each cut
+ * by workspace_limit as the *BatchHost calls are), pack, one download of the
+ * pack area and one of the pack sizes, header.  LZMA and PPMd7 have no tight
+ * bound: a stream gets a slot of len + len / 128 + 64 bytes first (incompressible
+ * streams above about 9 KiB outgrow it: LZMA's fast mode adds 1.45 %); the streams
+ * that report SZ_ERROR_OUTPUT_EOF are encoded again in one more batch per kind,
+ * at most twice (PPMd7 with its packed_len, LZMA with len + len / 3 + 128, then
+ * 2 * len + 1024), after which the call fails with SZ_ERROR_FAIL.
+ * ENCODE_HEADER: the header is one more LZMA folder (level 4, lc3 lp0 pb2, with
+ * a folder CRC) after the pack area, encoded by the same batch path in a
+ * second launch of one stream -- one lane, about 0.5 MB/s -- and the archive
+ * ends in the kEncodedHeader stub.
+ * *destLen in: capacity, out: the archive's size.  SZ_ERROR_OUTPUT_EOF when dest
+ * is short: *destLen = the needed size and dest is not written.  The plan's
+ * errors come before anything touches the device; SZ_ERROR_FAIL without a
+ * device (there is no CPU fallback).  options and stats may be NULL. */
+SRes LzmaGpu_7zWrite(Byte *dest, SizeT *destLen, const Byte *src, size_t src_size,
+                     const LzmaGpu7zItem *items, size_t n, const UInt16 *names, size_t names_len,
+                     const LzmaGpu7zMethod *methods, size_t n_methods,
+                     const LzmaGpu7zWriteOptions *options, LzmaGpu7zWriteStats *stats);
+
+/* The pack stage on the device (csrc/sevenz_pack_device.h).  Piece i's bytes
+ * start at bases[base] + off; its length is `len` for a Copy range, else the
+ * dest_len of result `slot` of its kind's result array.  Pieces of a folder are
+ * consecutive.  LAST: a 0x00 follows the piece (the last of an LZMA2 folder). */
+#define LZMA_GPU_7Z_PACK_COPY 0u
+#define LZMA_GPU_7Z_PACK_LZMA 1u
+#define LZMA_GPU_7Z_PACK_LZMA2 2u
+#define LZMA_GPU_7Z_PACK_PPMD 3u
+#define LZMA_GPU_7Z_PACK_LAST 1u
+#define LZMA_GPU_7Z_PACK_BASES 4
+typedef struct SzGpuPackPiece {   /* 32 bytes */
+  uint64_t off;
+  uint64_t len;      /* Copy only */
+  uint32_t slot;
+  uint32_t folder;
+  uint16_t kind;     /* LZMA_GPU_7Z_PACK_COPY .. PPMD */
+  uint16_t base;     /* index into bases */
+  uint32_t flags;    /* LZMA_GPU_7Z_PACK_LAST */
+} SzGpuPackPiece;
+
+/* All pointers device memory, bases 16-byte aligned (unused ones NULL); d_out
+ * may not overlap a base.  d_scratch: SzGpu_PackScratch(n) uint64.  Outputs:
+ * d_piece_off[i] = piece i's place in d_out (an exclusive scan of the lengths,
+ * LAST pieces counting one more), d_folder_size[f] = folder f's pack size (only
+ * on SZ_OK; a folder without pieces is not written), d_total: res = the first
+ * piece's that is not SZ_OK (_pad = its index; SZ_ERROR_PARAM for a kind, base,
+ * slot or folder out of range), else SZ_ERROR_OUTPUT_EOF when the total exceeds
+ * out_cap, else SZ_OK; dest_len = the total.  d_out is written only on SZ_OK,
+ * and then only in [0, total). */
+typedef struct SzGpuPackArgs {    /* 152 bytes */
+  const SzGpuPackPiece *d_pieces;
+  uint64_t n, n_folders;
+  const Byte *bases[LZMA_GPU_7Z_PACK_BASES];
+  const LzmaEncGpuResult *d_lzma;
+  uint64_t n_lzma;
+  const LzmaEncGpuResult *d_lzma2;
+  uint64_t n_lzma2;
+  const Ppmd7GpuEncResult *d_ppmd;
+  uint64_t n_ppmd;
+  Byte *d_out;
+  uint64_t out_cap;
+  uint64_t *d_scratch, *d_piece_off, *d_folder_size;
+  LzmaEncGpuResult *d_total;
+} SzGpuPackArgs;
+size_t SzGpu_PackScratch(size_t n);
+/* Four launches on `stream`, asynchronous.  SZ_OK if they were queued,
+ * SZ_ERROR_PARAM for n above 2^31 - 1, SZ_ERROR_FAIL without a device. */
+SRes SzGpu_PackBatch(const SzGpuPackArgs *args, void *stream);
+
 /* Device / diagnostics. */
 int LzmaGpu_DeviceCount(void);
 const char *LzmaGpu_LastError(void);

@@ -269,6 +269,52 @@ class SzFile(ctypes.Structure):
                 ("name_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+
+class SzItem(ctypes.Structure):
+    """LzmaGpu7zItem (include/lzma_gpu.h): one entry of an archive to write."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("size", ctypes.c_uint64),
+                ("name_off", ctypes.c_uint32), ("name_len", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("method", ctypes.c_uint32)]
+
+
+class SzMethod(ctypes.Structure):
+    """LzmaGpu7zMethod: one row of the writer's method table."""
+    _fields_ = [("method", ctypes.c_uint64), ("filter", ctypes.c_uint32),
+                ("ppmd_order", ctypes.c_uint32), ("ppmd_mem_size", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("props", CLzma2EncProps)]
+
+
+class SzWriteOptions(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("workspace_limit", ctypes.c_uint64)]
+
+
+class SzWriteStats(ctypes.Structure):
+    _fields_ = [("folders", ctypes.c_uint64), ("pieces", ctypes.c_uint64),
+                ("reencoded", ctypes.c_uint64), ("pack_bytes", ctypes.c_uint64),
+                ("header_bytes", ctypes.c_uint64), ("encode_launches", ctypes.c_uint64),
+                ("stage_ns", ctypes.c_uint64 * 8)]
+
+
+class SzPackPiece(ctypes.Structure):
+    """SzGpuPackPiece: one piece of the pack stage's table."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("slot", ctypes.c_uint32),
+                ("folder", ctypes.c_uint32), ("kind", ctypes.c_uint16), ("base", ctypes.c_uint16),
+                ("flags", ctypes.c_uint32)]
+
+
+class SzPackArgs(ctypes.Structure):
+    """SzGpuPackArgs: device pointers as integers."""
+    _fields_ = [("d_pieces", ctypes.c_void_p), ("n", ctypes.c_uint64),
+                ("n_folders", ctypes.c_uint64), ("bases", ctypes.c_void_p * 4),
+                ("d_lzma", ctypes.c_void_p), ("n_lzma", ctypes.c_uint64),
+                ("d_lzma2", ctypes.c_void_p), ("n_lzma2", ctypes.c_uint64),
+                ("d_ppmd", ctypes.c_void_p), ("n_ppmd", ctypes.c_uint64),
+                ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_uint64),
+                ("d_scratch", ctypes.c_void_p), ("d_piece_off", ctypes.c_void_p),
+                ("d_folder_size", ctypes.c_void_p), ("d_total", ctypes.c_void_p)]
+
+
 assert ctypes.sizeof(XzBlock) == 104 and ctypes.sizeof(Bcj2Job) == 80
 assert ctypes.sizeof(SzFolder) == 80 and ctypes.sizeof(SzFile) == 48
 assert ctypes.sizeof(StreamDesc) == 48 and ctypes.sizeof(Result) == 24
@@ -280,6 +326,9 @@ assert ctypes.sizeof(Ppmd7StreamDesc) == 48 and ctypes.sizeof(Ppmd7Result) == 24
 assert ctypes.sizeof(Ppmd7EncDesc) == 48 and ctypes.sizeof(Ppmd7EncResult) == 24
 assert ctypes.sizeof(CLzmaEncProps) == 48
 assert ctypes.sizeof(EncStreamDesc) == 72 and ctypes.sizeof(EncResult) == 16
+assert ctypes.sizeof(SzItem) == 32 and ctypes.sizeof(SzMethod) == 88
+assert ctypes.sizeof(SzWriteOptions) == 16 and ctypes.sizeof(SzWriteStats) == 112
+assert ctypes.sizeof(SzPackPiece) == 32 and ctypes.sizeof(SzPackArgs) == 152
 
 _P = ctypes.c_void_p
 _sig = {
@@ -408,6 +457,18 @@ _sig = {
                                        ctypes.POINTER(ISeqInStream), _P]),
     "LzmaGpu_XzEncode": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t,
                                         ctypes.POINTER(CLzma2EncProps), ctypes.c_uint]),
+    "LzmaGpu_7zWritePlan": (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _P,
+                                           ctypes.c_size_t, _P, ctypes.c_size_t, _sp, _sp,
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "LzmaGpu_7zWriteHeader": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P,
+                                             ctypes.c_size_t, ctypes.c_uint, _P, ctypes.c_size_t,
+                                             _sp, _P, ctypes.c_uint64]),
+    "LzmaGpu_7zWrite": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P,
+                                       ctypes.c_size_t, _P, ctypes.c_size_t,
+                                       ctypes.POINTER(SzWriteOptions),
+                                       ctypes.POINTER(SzWriteStats)]),
+    "SzGpu_PackScratch": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "SzGpu_PackBatch": (ctypes.c_int, [ctypes.POINTER(SzPackArgs), _P]),
     "LzmaGpu_DeviceCount": (ctypes.c_int, []),
     "LzmaGpu_LastError": (ctypes.c_char_p, []),
     "LzmaGpu_Version": (ctypes.c_char_p, []),
@@ -932,6 +993,132 @@ def SzExtract(data, dest_cap, max_files=1 << 16, flags=0):
     r = _lib.LzmaGpu_7zExtractEx(out, ctypes.byref(dl), _buf(data), len(data), fres, max_files,
                                  flags)
     return r, out.raw[:dl.value], list(fres)
+
+
+# ---------------------------------------------------------------- 7z writing
+
+SZ_ITEM_DIR, SZ_ITEM_JOIN = 1, 2
+SZ_WRITE_ENCODE_HEADER, SZ_WRITE_TIMINGS = 1, 2
+SZ_STAGES = ("upload", "crc", "filter", "encode", "pack", "download", "header", "total")
+SZ_HEADER_STUB = 1
+SZ_M_COPY, SZ_M_LZMA, SZ_M_LZMA2, SZ_M_PPMD = 0, 0x030101, 0x21, 0x030401
+SZ_FILTER_X86, SZ_FILTER_ARM = 4, 7
+SZ_PACK_COPY, SZ_PACK_LZMA, SZ_PACK_LZMA2, SZ_PACK_PPMD = 0, 1, 2, 3
+SZ_PACK_LAST = 1
+
+
+def sz_method(method=SZ_M_LZMA, filter=0, level=1, dict_size=0, lc=-1, lp=-1, pb=-1,
+              block_size=0, order=6, mem_size=1 << 20):
+    """One LzmaGpu7zMethod row: the LZMA / LZMA2 props as enc2_props gives them."""
+    m = SzMethod()
+    m.method, m.filter, m.ppmd_order, m.ppmd_mem_size = method, filter, order, mem_size
+    m.props = enc2_props(level, dict_size, lc, lp, pb, block_size)
+    return m
+
+
+def sz_items(entries):
+    """entries: (name, src_off, size, flags, method index).  Returns the SzItem
+    array and the names buffer (a ctypes uint16 array, NUL after every name)."""
+    arr = (SzItem * max(len(entries), 1))()
+    units = []
+    for i, (name, off, size, flags, method) in enumerate(entries):
+        raw = name.encode("utf-16-le")
+        u = [int.from_bytes(raw[k:k + 2], "little") for k in range(0, len(raw), 2)] + [0]
+        it = arr[i]
+        it.src_off, it.size, it.flags, it.method = off, size, flags, method
+        it.name_off, it.name_len = len(units), len(u)
+        units += u
+    names = (ctypes.c_uint16 * max(len(units), 1))(*units)
+    return arr, names, len(units)
+
+
+def _array(ctype, rows):
+    arr = (ctype * max(len(rows), 1))()
+    for i, r in enumerate(rows):
+        ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(r), ctypes.sizeof(ctype))
+    return arr
+
+
+def sz_write_plan(items, n, src_size, names_len, methods):
+    """LzmaGpu_7zWritePlan: (res, [SzFolder...], n_pieces, dest_bound)."""
+    marr = _array(SzMethod, methods)
+    nfo, npc = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    bound = ctypes.c_uint64(0)
+    args = (items, n, src_size, names_len, marr, len(methods))
+    r = _lib.LzmaGpu_7zWritePlan(*args, None, 0, ctypes.byref(nfo), ctypes.byref(npc),
+                                 ctypes.byref(bound))
+    if r != SZ_OK:
+        return r, [], 0, 0
+    fo = (SzFolder * max(nfo.value, 1))()
+    r = _lib.LzmaGpu_7zWritePlan(*args, fo, nfo.value, ctypes.byref(nfo), ctypes.byref(npc),
+                                 ctypes.byref(bound))
+    return r, list(fo)[:nfo.value], npc.value, bound.value
+
+
+def sz_write_header(folders, items, n, file_crcs, names, names_len, flags=0, pack_area_size=0):
+    """LzmaGpu_7zWriteHeader: (res, header bytes, the 32-byte signature header)."""
+    farr = _array(SzFolder, folders)
+    crcs = (ctypes.c_uint32 * max(n, 1))(*file_crcs) if file_crcs is not None else None
+    hl = ctypes.c_size_t(0)
+    sig = ctypes.create_string_buffer(32)
+    r = _lib.LzmaGpu_7zWriteHeader(farr, len(folders), items, n, crcs, names, names_len, flags,
+                                   None, 0, ctypes.byref(hl), None, 0)
+    if r != SZ_ERROR_OUTPUT_EOF:
+        return r, b"", b""
+    out = ctypes.create_string_buffer(max(hl.value, 1))
+    r = _lib.LzmaGpu_7zWriteHeader(farr, len(folders), items, n, crcs, names, names_len, flags,
+                                   out, hl.value, ctypes.byref(hl), sig, pack_area_size)
+    return r, out.raw[:hl.value], sig.raw
+
+
+def SzWrite(src, items, n, names, names_len, methods, dest_cap, flags=0, workspace_limit=0,
+            fill=0):
+    """LzmaGpu_7zWrite: (res, destLen, the whole dest buffer, SzWriteStats)."""
+    marr = _array(SzMethod, methods)
+    opt = SzWriteOptions(flags, 0, workspace_limit)
+    st = SzWriteStats()
+    d = ctypes.create_string_buffer(bytes([fill]) * max(dest_cap, 1), max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    r = _lib.LzmaGpu_7zWrite(d, ctypes.byref(dl), _buf(src), len(src), items, n, names, names_len,
+                             marr, len(methods), ctypes.byref(opt), ctypes.byref(st))
+    return r, dl.value, d.raw[:dest_cap], st
+
+
+def sz_pack_scratch(n):
+    return _lib.SzGpu_PackScratch(n)
+
+
+def sz_pack_batch_device(args, stream=0):
+    """SzGpu_PackBatch over an SzPackArgs of raw device pointers (ints)."""
+    return _lib.SzGpu_PackBatch(ctypes.byref(args), stream or None)
+
+
+def sevenz_compress(files, method=SZ_M_LZMA, filter=0, solid=0, encode_header=False, level=1,
+                    dict_size=0, block_size=0, order=6, mem_size=1 << 20):
+    """A 7z archive of `files`, (name, bytes | None) pairs (None: a directory),
+    every file with data a folder of its own, or `solid` files per folder.
+    Returns the archive bytes; raises on an error."""
+    entries, src, run = [], bytearray(), 0
+    for name, data in files:
+        if data is None:
+            entries.append((name, 0, 0, SZ_ITEM_DIR, 0))
+            continue
+        join = SZ_ITEM_JOIN if (len(data) and solid > 1 and run % solid) else 0
+        entries.append((name, len(src), len(data), join, 0))
+        if len(data):
+            run += 1
+        src += data
+    items, names, names_len = sz_items(entries)
+    methods = [sz_method(method, filter, level, dict_size, block_size=block_size, order=order,
+                         mem_size=mem_size)]
+    r, _, _, bound = sz_write_plan(items, len(entries), len(src), names_len, methods)
+    if r != SZ_OK:
+        raise RuntimeError(f"LzmaGpu_7zWritePlan: {r}: {last_error()}")
+    flags = SZ_WRITE_ENCODE_HEADER if encode_header else 0
+    r, n, out, _ = SzWrite(bytes(src), items, len(entries), names, names_len, methods, bound, flags)
+    if r != SZ_OK:
+        raise RuntimeError(f"LzmaGpu_7zWrite: {r}: {last_error()}")
+    return out[:n]
 
 
 # ---------------------------------------------------------------- PPMd7 batches
