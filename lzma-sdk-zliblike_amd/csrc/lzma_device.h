@@ -757,6 +757,45 @@ __host__ __device__ constexpr bool lit_addr_on() {
   constexpr uint32_t k = (M & kDupBit) != 0u ? 1u : (M & kCoopBit) != 0u ? 2u : 4u;
   return ((M >> S_LITP) & 1u) != 0u && (LZGPU_LIT_ADDR & k) != 0u;
 }
+// Fused tree walks (round 7): lanes of a wave that need the same
+// kind of walk over different cells take it in ONE code region on a per-lane
+// base, instead of one EXEC-masked region per case after the other -- the wave
+// pays every region's whole decision chain, whatever number of lanes use it.
+// A fusion moves where a lane's decision is issued, never which decisions the
+// lane makes or their order.  One bit per fusion:
+//   1 (F1) length coder: LenLow and LenMid are one sub3 on a per-lane base
+//   2 (F2) distance tail: SpecPos and Align are one reverse-tree walk with a
+//          per-lane (base, bit count), behind the direct bits
+//   8 (F4) literal: in an iteration where some lane decodes a matched literal,
+//          all literal lanes take one 8-level walk (matched lanes from their
+//          preloaded matched cells until the first mismatch)
+// (4, F3, the rep chain by level, was not built; LenHigh's top three levels in
+// F1's walk measured +0.8 %, inside three times the A/B spread, and were
+// removed: DESIGN.md §4 round 7.)  Compiled only into the
+// throughput placement, both row layouts: every other kernel's lanes either
+// agree (one-stream, cooperative, sessions), where a per-lane select is pure
+// cost, or were not measured (generic batch kernel, latency placement).
+#ifndef LZGPU_FUSE
+#define LZGPU_FUSE 11
+#endif
+template <uint32_t M>
+__host__ __device__ constexpr bool fuse_on(uint32_t bit) {
+  return (LZGPU_FUSE & bit) != 0u && (M & ~kIlvBit) == LZGPU_LDS_MASK;
+}
+// Some active lane of the wave wants the fused walk.  The host emulation is
+// one lane wide: there -DLZGPU_FUSE_EMU_ALL=1 (tests only) answers "yes" for
+// every literal, so that lanes which only follow a neighbour into the walk --
+// plain literals in it -- are emulated too.
+#ifndef LZGPU_FUSE_EMU_ALL
+#define LZGPU_FUSE_EMU_ALL 0
+#endif
+__device__ __forceinline__ bool lz_fuse_any(bool v) {
+#ifdef LZGPU_HOST_EMU
+  return v || LZGPU_FUSE_EMU_ALL != 0;
+#else
+  return __builtin_amdgcn_ballot_w64(v) != 0;
+#endif
+}
 // LDS cell addresses as integers (32-bit on the device)
 #ifdef LZGPU_HOST_EMU
 typedef uintptr_t lds_addr_t;
@@ -979,6 +1018,35 @@ struct Rc {
     range = b ? range - bound : bound;
     code = b ? code - bound : code;
     return b;
+    }
+  }
+  // The decision's value part alone -- decide_b's arithmetic with the cell's
+  // new value returned in pn instead of stored: the fused literal walk
+  // (lz_literal, fuse_on) stores it to the cell of the lane's class.  Kept
+  // beside decide_b instead of under it, so that the kernels without fused
+  // walks compile exactly as before.
+  __device__ __forceinline__ bool decide_v(uint32_t p, uint16_t& pn) {
+    const uint32_t bound = (range >> 11) * p;
+    if constexpr (F) {
+      uint32_t t;
+      const bool borrow = __builtin_sub_overflow(code, bound, &t);
+      code = borrow ? code : t;
+      range = borrow ? bound : range - bound;
+#if LZGPU_BIT16
+      const uint16_t p16 = uint16_t(p);
+      const uint16_t c16 = borrow ? uint16_t(2048) : uint16_t(31);
+      pn = uint16_t(uint16_t(p16 * uint16_t(31) + c16) >> 5);
+#else
+      pn = uint16_t((p * 31u + (borrow ? 2048u : 31u)) >> 5);
+#endif
+      return !borrow;
+    } else {
+      const bool b = code >= bound;
+      const int32_t m = b ? 0 : int32_t(kProbOne - 31);
+      pn = uint16_t(int32_t(p) - ((int32_t(p) - m) >> 5));
+      range = b ? range - bound : bound;
+      code = b ? code - bound : code;
+      return b;
     }
   }
   template <class P>
@@ -1537,7 +1605,61 @@ __device__ __forceinline__ void lz_literal(Rc<Rd, U, F>& rc, const Tab<M, Lo>& T
   // prev and total are 0 then, so the formula gives it without a test)
   const uint32_t ctx = ((total & lp_mask) << lc) + (prev >> (8 - lc));
   (void)full;
-  if (lz_br<U>(st < 7)) {
+  constexpr bool kFuseLit = fuse_on<M>(8u) && lit_addr_on<M>() && mb_pf_on<M>() &&
+                            ((M >> S_LITM) & 1u) == 0u;
+  if constexpr (kFuseLit) {
+    // F4 (fuse_on): an iteration in which some literal lane of the wave is
+    // in a matched state -- one per pass of the symbol loop, the first after a
+    // match -- takes ONE 8-level walk for all of them; every other iteration
+    // is the plain walk alone.  The plain tree's address walk runs in every
+    // lane: a = the plain cell of the bits decided so far, which is exactly
+    // where a matched lane continues after its first mismatch (offs = 0 in the
+    // reference).  While a lane is still on its matched cells its probability
+    // is the preloaded pk[k] and its update goes to that global cell; its LDS
+    // cell is read and written back unchanged.
+    auto lp = T.template at<S_LITP>(ctx << 8);
+    typedef decltype(lp) P;
+    if (lz_fuse_any(st >= 7)) {
+      const bool ml = st >= 7;
+      st = ml ? ((st < 10) ? st - 3 : st - 6) : ((st < 4) ? 0 : st - 3);
+      // a plain lane loads (and never uses) the cells of match byte 0
+      const uint32_t mb = ml ? (mb_pf & 0xFFu) : 0u;
+      auto lm = T.template at<S_LITM>(ctx << 9);
+      uint32_t pk[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        pk[k] = lm[(((mb >> (7 - k)) & 1u) << 8) + ((1u << k) | (mb >> (8 - k)))];
+      LZ_WCLS(rc, W_MLIT);
+      rc.wstamp();
+      constexpr lds_addr_t stp = kLdsStep<P>;
+      const lds_addr_t base = lds_addr_of(lp);
+      lds_addr_t k0 = lds_addr_t(0) - base, k1 = stp - base;
+      lz_opaque(k1);
+      lds_addr_t a = base + stp;
+      bool matched = ml;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint32_t mk = (mb >> (7 - k)) & 1u;
+        if (k == 4) rd_topup(*rc.rd);
+        const P cell = lds_at<P>(a);
+        const uint32_t pl = *cell;
+        const uint32_t p = matched ? pk[k] : pl;
+        rc.norm_u();
+        uint16_t pn;
+        const uint32_t b = rc.decide_v(p, pn) ? 1u : 0u;
+        // (while matched, the symbol is the match byte's top k bits under a
+        // leading 1: the cell loaded above)
+        if (matched) lm[(mk << 8) + ((1u << k) | (mb >> (8 - k)))] = pn;
+        *cell = matched ? uint16_t(pl) : pn;
+        matched = matched && (b == mk);
+        a = (a << 1) + (b ? k1 : k0);
+      }
+      sym = uint32_t((a - base) / stp);
+    } else {
+      st = (st < 4) ? 0 : st - 3;
+      sym = rc.tree8_a(lp);
+    }
+  } else if (lz_br<U>(st < 7)) {
     st = (st < 4) ? 0 : st - 3;
     auto lp = T.template at<S_LITP>(ctx << 8);
     if constexpr (lit_addr_on<M>()) {
@@ -1889,6 +2011,22 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           LZ_WCLS(rc, W_LENHI);
           len = 16 + rc.tree8_g(T.template at<S_LENHI>(lcoder_is_rep << 8)) - 256;
         }
+        } else if constexpr (fuse_on<M>(1u)) {
+        // F1: choice, then choice2 for the lanes behind choice = 1, then ONE
+        // 3-level walk for every lane with a short length -- the low tree or
+        // the mid tree by a per-lane base and offset
+        const uint32_t ch = lbase[0];
+        rc.wstamp();
+        const uint32_t c1 = rc.bit_v(ch, lbase);
+        uint32_t c2 = 0;
+        if (c1) c2 = rc.bit(lbase + 1);
+        if (!c2) {
+          auto len_t = lbase + (2 + (c1 ? (8u << pb) : 0u) + (ps << 3));
+          len = (c1 ? 8u : 0u) + rc.sub3(len_t, 1) - 8;
+        } else {
+          LZ_WCLS(rc, W_LENHI);
+          len = 16 + rc.template tree<8>(T.template at<S_LENHI>(lcoder_is_rep << 8));
+        }
         } else {
         const uint32_t ch = lbase[0];
         auto lo_t = lbase + 2 + (ps << 3);
@@ -1952,7 +2090,55 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
         const uint32_t slot = dist;
         uint32_t nbits = (slot >> 1) - 1;
         dist = 2 | (slot & 1);
-        if (lz_br<kU>(slot < 14)) {
+        constexpr bool kFuseTail = fuse_on<M>(2u) && ((M >> S_SPEC) & 1u) == 0u &&
+                                   ((M >> S_ALIGN) & 1u) == 0u;
+        if constexpr (kFuseTail) {
+          // F2: the direct bits first (slot >= 14), then ONE reverse-tree walk
+          // for every lane on a per-lane (base, bit count): SpecPos with
+          // (slot >> 1) - 1 bits, or Align with 4 -- three levels from one load
+          // batch where the lane has that many, the rest one by one
+          const bool spec = slot < 14;
+          uint32_t rb_off, rb_n;
+          if (!spec) {
+            nbits -= 4;
+            do rc.direct(dist); while (--nbits != 0);
+            dist <<= 4;
+            rb_off = T.L.o[S_ALIGN];
+            rb_n = 4;
+          } else {
+            dist <<= nbits;
+            rb_off = T.L.o[S_SPEC] + (dist - slot - 1);
+            rb_n = nbits;
+          }
+#if LZGPU_PROF == 1 && !defined(LZGPU_HOST_EMU)
+          const uint64_t t_al = lz_clock();
+          s.prof[6] += t_al - t_tail;  // direct bits
+#endif
+          LZ_WCLS(rc, W_SPEC);
+          auto rb_t = T.g(rb_off);
+          uint32_t mask = 1, node = 1;
+          if (rb_n >= 3) {
+            node = rc.sub3(rb_t, 1);
+            dist |= ((node >> 2) & 1u) | (((node >> 1) & 1u) << 1) | ((node & 1u) << 2);
+            mask = 8;
+            rb_n -= 3;
+          }
+          while (rb_n != 0) {
+            const uint32_t b = rc.bit(rb_t + node);
+            node = (node << 1) | b;
+            dist |= b ? mask : 0u;
+            mask <<= 1;
+            --rb_n;
+          }
+#if LZGPU_PROF == 1 && !defined(LZGPU_HOST_EMU)
+          s.prof[7] += lz_clock() - t_al;  // the fused SpecPos / Align walk
+#endif
+          if (!spec && dist == 0xFFFFFFFFu) {
+            len += kLenDone;
+            st -= 12;
+            break;
+          }
+        } else if (lz_br<kU>(slot < 14)) {
           dist <<= nbits;
           uint32_t mask = 1, node = 1;
           const uint32_t sp = dist - slot - 1;
