@@ -250,6 +250,18 @@ def test_emu_fuzz_vs_oracle(emu, lds):
         assert got == exp[k][:4] and out == exp[k][4], (k, got, exp[k][:4])
 
 
+def test_emu_handmade_set(emu):
+    """The hand-made streams (tests/handmade_cases.py: symbols and chunk
+    sequences no encoder writes, both finish modes, 16 source alignments for
+    the short ones) through this build, against the reference's answers."""
+    import handmade_cases as H
+    its = H.items()
+    descs, src, _ = H.batch(its)
+    res, dst = run_batch(emu, descs, src, lds=True)
+    bad = H.mismatches(its, descs, res, dst)
+    assert not bad, (len(bad), bad[:8])
+
+
 def test_update_forms_agree_for_every_probability():
     """Rc::decide's two update forms equal the reference's UPDATE_0 / UPDATE_1
     (LzmaDec.c:12-16) for every probability a cell can hold (0..2048)."""

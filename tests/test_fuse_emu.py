@@ -82,6 +82,17 @@ def test_fuse_emu_golden_lzma(emu):
     assert not bad, bad[:10]
 
 
+def test_fuse_emu_handmade_set(emu):
+    """The hand-made streams (tests/handmade_cases.py) through every fusion
+    build, against the reference's answers."""
+    import handmade_cases as H
+    its = H.items()
+    descs, src, _ = H.batch(its)
+    res, dst = run_batch(emu, descs, src, True)
+    bad = H.mismatches(its, descs, res, dst)
+    assert not bad, (len(bad), bad[:8])
+
+
 _FUZZ = None
 
 

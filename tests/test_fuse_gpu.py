@@ -421,3 +421,82 @@ def test_fused_walks_bit_exact(props, ilv, n):
         if got != tuple(e[:4]) or out != e[4]:
             bad.append((k, got, e[:4]))
     assert not bad, (props, ilv, n, len(bad), bad[:6])
+
+
+# ------------------------------------------------------------------ hand-made neighbours
+
+_HAND = {}
+
+
+def handmade_wave(lc, pb, n):
+    """n lanes made only of hand-made cases (tests/handmade_cases.py) under
+    lc / lp0 / pb: lanes that decode 5,000 bytes beside lanes that end in a
+    data error at once, at the dictionary edge or at the capacity, lanes that
+    end at an end marker of each length, and symbols against fully trained
+    contexts.  Returns (H, [(case, finish, None)], descs, src, dst bytes)."""
+    if (lc, pb, n) not in _HAND:
+        import handmade_cases as H
+        tag = f" lc{lc}lp0pb{pb}"
+        by = {c["name"]: c for c in H.lzma_cases()}
+        pick = [(f"5000 literals, distance index {i}", 1) for i in (4094, 4095, 4096, 5000)]
+        pick += [("5000 literals, index 4095 then rep0-long", 1)]
+        pick += [(f"end marker length {ln}, three bytes behind, cap+0", f)
+                 for ln in H.MARKER_LENS for f in (0, 1)]
+        pick += [(f"first symbol {k}", 0) for k in ("rep0", "rep1", "rep2", "rep3", "short rep")]
+        pick += [("50 literals, distance index 49", 1), ("50 literals, distance index 50", 1),
+                 ("length 273 over the capacity", 0), ("length 273 over the capacity", 1),
+                 ("matched literals, every state and level", 1), ("state walk", 0),
+                 ("reps on initial values", 1), ("hungry rep3 at window fill 1", 1),
+                 ("hungry match at window fill 4", 0), ("hungry short_rep at window fill 8", 1),
+                 ("copy distance 1 length 273 to the capacity", 1),
+                 ("copy distance 3 length 17 one over the capacity", 1),
+                 ("copy distance 17 length 273 one over the capacity", 0),
+                 ("copy distance 8 length 2 to the capacity", 0),
+                 ("capacity 0, stream not empty", 1)]
+        assert len(pick) == 33
+        # the long lanes spread among the short ones
+        pick = pick[5:5 + (n - 5) // 2] + pick[:5] + pick[5 + (n - 5) // 2:n]
+        its = [(by[name + tag], f, None) for name, f in pick]
+        _HAND[lc, pb, n] = (H, its) + H.batch(its)
+    return _HAND[lc, pb, n]
+
+
+@pytest.mark.parametrize("props", [(0, 0), (3, 2)])
+def test_handmade_wave_is_what_it_claims(props):
+    """On the CPU: one class of 32 lanes per group in both row layouts, and in
+    it lanes of 5,000 bytes, error lanes and end-marker lanes."""
+    import lzmagpu as L
+    for n in (32, 33):
+        H, its, items, src, dst_bytes = handmade_wave(props[0], props[1], n)
+        assert len(its) == n
+        rows = [H.expected(c, f)[0] for c, f, _ in its]
+        assert sum(1 for r in rows if r[0] == 0 and r[2] >= 5000) >= 3
+        assert sum(1 for r in rows if r[0] == 1) >= 10
+        assert sum(1 for r in rows if r[:2] == (0, 1)) >= 4
+        for ilv in (True, False):
+            plan, order = L.plan_ex(L.make_descs(items), _opts(L, ilv))
+            assert plan.n_lds == n and plan.n_classes == 1
+            c = plan.classes[0]
+            assert c.lds_mask == M_THR | (ILV if ilv else 0) and c.lanes_per_group == LANES
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [32, 33])
+@pytest.mark.parametrize("ilv", [True, False])
+@pytest.mark.parametrize("props", [(0, 0), (3, 2)])
+def test_fused_walks_handmade_neighbours(props, ilv, n):
+    """One wave of 32 and a batch of 33 (a second wave with one live lane) of
+    hand-made cases on the throughput instantiation: lanes that stop at once
+    beside lanes that go on for 5,000 bytes, every row and byte against the
+    reference's."""
+    import lzmagpu as L
+    if L.device_count() <= 0:
+        pytest.fail("no HIP device visible: " + L.last_error())
+    H, its, items, src, dst_bytes = handmade_wave(props[0], props[1], n)
+    plan = L.Plan()
+    r, res, dst = L.decode_batch_host(L.make_descs(items), src, dst_bytes, _opts(L, ilv), plan)
+    assert r == 0, L.last_error()
+    assert plan.n_classes == 1 and plan.classes[0].lds_mask == M_THR | (ILV if ilv else 0)
+    assert plan.classes[0].lanes_per_group == LANES
+    bad = H.mismatches(its, items, res, dst)
+    assert not bad, (props, ilv, n, len(bad), bad[:6])

@@ -178,6 +178,54 @@ def test_goldens_through_each_kernel(L, kernel):
     assert not bad, (kernel, len(bad), bad[:8])
 
 
+# ---------------------------------------------------------------- hand-made streams, every kernel
+
+@pytest.fixture(scope="module")
+def handmade():
+    """tests/handmade_cases.py: every LZMA and LZMA2 case, both finish modes,
+    the short inputs at each of the 16 source alignments; generated, and the
+    expected results (the reference's) looked up, once for all kernels."""
+    import handmade_cases as H
+    its = H.items()
+    for c, finish, _ in its:
+        H.expected(c, finish)
+    return (H, its) + H.batch(its)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_handmade_through_each_kernel(L, torch, handmade, kernel):
+    """Symbols and chunk sequences no encoder writes (a rep first, distances at
+    the dictionary edge, end markers of any length, props changes, a 0x80 chunk
+    behind a stored one, padded pack sizes, symbols against fully trained
+    contexts at every reader-window fill ...) through each instantiation in
+    one batch: every result row and output byte equals the reference's, and
+    over a destination filled with 0xA5 nothing is written behind a stream's
+    dest_len."""
+    H, its, items, src, dst_bytes = handmade
+    descs = L.make_descs(items)
+    plan = L.Plan()
+    r, res, dst = L.decode_batch_host(descs, src, dst_bytes, _opts(L, kernel), plan)
+    assert r == 0, L.last_error()
+    _check_plan(plan, kernel)
+    if kernel in THR:
+        # the lc0/lp0/pb0 class runs the config-3 launch shape: 32 streams per wave
+        lc0 = sum(1 for c, _, _ in its if c["kind"] == "lzma" and c["props"][0] == 0)
+        assert any(plan.classes[k].lanes_per_group == 32 and plan.classes[k].n == lc0
+                   for k in range(plan.n_classes))
+    bad = H.mismatches(its, items, res, dst)
+    assert not bad, (kernel, len(bad), bad[:8])
+    # the same batch over device buffers with a poisoned destination
+    plan2, res2, d_dst = _device_decode(L, torch, descs, np.frombuffer(src, np.uint8), dst_bytes,
+                                        _opts(L, kernel), fill=0xA5)
+    _check_plan(plan2, kernel)
+    out = d_dst.cpu().numpy().tobytes()
+    rows = [L.Result(int(x["res"]), int(x["status"]), int(x["dest_len"]), int(x["src_len"]))
+            for x in res2]
+    bad = H.mismatches(its, items, rows, out, poison=0xA5)
+    assert not bad, (kernel, "poisoned destination", len(bad), bad[:8])
+    assert out[dst_bytes:] == b"\xa5" * 16
+
+
 # ---------------------------------------------------------------- the stream's last bytes
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -362,15 +410,16 @@ def test_lzma2_fuzz_vs_oracle_each_kernel(L, kernel):
 
 # ---------------------------------------------------------------- full-size configs
 
-def _device_decode(L, torch, descs, comp, dst_bytes, opts=None):
+def _device_decode(L, torch, descs, comp, dst_bytes, opts=None, fill=0):
     """LzmaGpu_PlanBatch{Ex,Opt} + LzmaGpu_DecodeBatchEx over device buffers
-    (the bench's path).  Returns (plan, results, d_dst)."""
+    (the bench's path); the destination starts out as `fill` bytes.  Returns
+    (plan, results, d_dst)."""
     plan, order = L.plan_ex(descs, opts)
     dev = torch.device("cuda", 0)
     n = len(descs)
     d_src = torch.from_numpy(np.concatenate([np.asarray(comp, np.uint8),
                                              np.zeros(16, np.uint8)])).to(dev)
-    d_dst = torch.zeros(dst_bytes + 16, dtype=torch.uint8, device=dev)
+    d_dst = torch.full((dst_bytes + 16,), fill, dtype=torch.uint8, device=dev)
     d_ws = torch.empty(max(int(plan.workspace_bytes), 16), dtype=torch.uint8, device=dev)
     d_desc = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
     d_order = torch.frombuffer(bytearray(bytes(order)), dtype=torch.uint8).to(dev)

@@ -291,3 +291,51 @@ def test_lzma2_blocks_batch(L):
     # and the whole stream through the one-call GPU LZMA2 path
     res1 = L.Lzma2Decode(comp, 16, doff, 1)
     assert res1[:4] == (0, 1, doff, len(comp)) and res1[4] == dst
+
+
+# ---------------------------------------------------------------- hand-made streams, drop-ins
+
+def test_handmade_one_call_dropins(L):
+    """Every hand-made case (tests/handmade_cases.py: symbols and chunk
+    sequences no encoder writes) through the one-call drop-ins, one call each
+    per finish mode: LzmaDecode and Lzma2Decode against the reference's rows
+    and output."""
+    import handmade_cases as H
+    bad = []
+    for c in H.cases():
+        for finish in (0, 1):
+            want, digest = H.expected(c, finish)
+            if c["kind"] == "lzma":
+                got = L.LzmaDecode(c["src"], c["props"], c["cap"], finish)
+            else:
+                got = L.Lzma2Decode(c["src"], c["prop"], c["cap"], finish)
+                # Lzma2Decode maps an OK / NEEDS_MORE_INPUT ending of the
+                # DecodeToDic loop to SZ_ERROR_INPUT_EOF (Lzma2Dec.c:350-351)
+                if want[:2] == (0, 3):
+                    want = (6,) + want[1:]
+            if tuple(got[:4]) != want or H.sha(got[4]) != digest:
+                bad.append((c["name"], finish, got[:4], want))
+    assert not bad, (len(bad), bad[:10])
+
+
+def test_handmade_streaming_small_cases(L):
+    """The LZMA cases of at most 100 output bytes (4 KiB dictionary) through
+    the LzmaDec_DecodeToBuf loop in chunks of 7 input and 13 output bytes:
+    the call trace and the output equal the reference's (the oracle's where the
+    reference is not built).  Larger cases stay out of this loop on purpose:
+    every call is a launch."""
+    import handmade_cases as H
+    lib, prefix = (native.ref(), "ref") if native.have_ref() else (native.oracle(), "orc")
+    cs = [c for c in H.lzma_cases() if c["cap"] <= 100 and
+          int.from_bytes(c["props"][1:5], "little") == H.DICT]
+    assert len(cs) >= 100 and {c["group"] for c in cs} >= {
+        "rep_first", "reps_initial", "edge_unfilled", "end_marker", "len273_over_cap", "overlap",
+        "empties"}
+    bad = []
+    for c in cs:
+        for finish in (0, 1):
+            want = native.stream_decode(lib, prefix, c["src"], c["props"], c["cap"], 7, 13, finish)
+            got = L.stream_decode(c["src"], c["props"], c["cap"], 7, 13, finish)
+            if got != want:
+                bad.append((c["name"], finish, got[0], want[0], got[1][-2:], want[1][-2:]))
+    assert not bad, (len(bad), bad[:6])
