@@ -5,12 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <exception>
-#include <numeric>
 #include <string.h>
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
+#include "host_batch.h"
 #include "lzma2enc_device.h"
 #include "lzma2enc_internal.h"
 #include "lzma_gpu_internal.h"
@@ -71,36 +70,20 @@ extern "C" SRes Lzma2EncGpu_DescFromProps(const CLzma2EncProps* props, LzmaEncGp
   return SZ_OK;
 }
 
-static uint64_t slice_bytes(const LzmaEncGpuStreamDesc& d) {
-  LzmaEncGpuStreamDesc t = d;
-  t.ws_off = 0;
-  if (lzma2enc_check(t) != lzenc::kOk) return 0;
-  return lzenc::lzma2enc_layout(lzmaenc_params(t), t.src_len).bytes;
-}
-
-static void longest_first(const LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order) {
-  std::iota(order, order + n, 0u);
-  std::stable_sort(order, order + n,
-                   [&](uint32_t a, uint32_t b) { return descs[a].src_len > descs[b].src_len; });
-}
-
 extern "C" SRes Lzma2EncGpu_PlanBatch(LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order,
                                       uint64_t* workspace_bytes) {
   if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  try {
+  return guarded("LZMA2 encode plan: host allocation failed", [&]() -> SRes {
     uint64_t at = 0;
     for (size_t i = 0; i < n; ++i) {
-      const uint64_t need = slice_bytes(descs[i]);
+      const uint64_t need = lzma2enc_slice_bytes(descs[i]);
       descs[i].ws_off = need ? at : 0;
       at += need;
     }
     if (workspace_bytes) *workspace_bytes = at;
-    if (order) longest_first(descs, n, order);
+    if (order) longest_first(n, [&](uint32_t i) { return descs[i].src_len; }, order);
     return SZ_OK;
-  } catch (const std::exception&) {
-    set_error("LZMA2 encode plan: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  });
 }
 
 extern "C" SRes Lzma2EncGpu_EncodeBatch(const LzmaEncGpuStreamDesc* d_descs,
@@ -139,76 +122,26 @@ extern "C" SRes Lzma2EncGpu_Compact(const LzmaEncGpuStreamDesc* d_descs,
 namespace {
 
 // The device side of one host call: the source, the blocks' slots, the
-// descriptors and results in the caller's index order.
-struct Batch {
-  DevArr<uint8_t> src, dst, ws;
-  DevArr<LzmaEncGpuStreamDesc> desc;
-  DevArr<LzmaEncGpuResult> res;
-  DevArr<uint32_t> order;
-};
+// descriptors and results in the caller's index order, the launch order.
+typedef HostBatch<LzmaEncGpuStreamDesc, LzmaEncGpuResult> Batch;
 
 // Uploads src (and dst when dst_init is given), lays the workspace out over
 // the longest-first order in as many launches as keep it at or under the
 // limit, and queues them on the null stream.  The caller synchronises.
 SRes run_batch(const LzmaEncGpuStreamDesc* descs, size_t n, const Byte* src, size_t src_size,
                const Byte* dst_init, size_t dst_size, uint64_t workspace_limit, Batch& b) {
-  if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  for (size_t i = 0; i < n; ++i) {
-    const LzmaEncGpuStreamDesc& d = descs[i];
-    if (d.src_off > src_size || d.src_len > src_size - d.src_off || d.dst_off > dst_size ||
-        d.dst_cap > dst_size - d.dst_off)
-      return SZ_ERROR_PARAM;
-  }
-  if (workspace_limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if (!hip_ok(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo")) return SZ_ERROR_FAIL;
-    workspace_limit = free_b / 2;
-  }
-  std::vector<uint32_t> order(n);
-  longest_first(descs, n, order.data());
-  std::vector<LzmaEncGpuStreamDesc> d(descs, descs + n);
-  std::vector<size_t> cut{0};
-  uint64_t ws_max = 0, ws_cur = 0;
-  for (size_t k = 0; k < n; ++k) {
-    LzmaEncGpuStreamDesc& t = d[order[k]];
-    const uint64_t need = slice_bytes(t);
-    if (need > workspace_limit) {
-      set_error("LZMA2 encode batch: one block's workspace slice exceeds the limit");
-      return SZ_ERROR_MEM;
-    }
-    if (ws_cur + need > workspace_limit) {
-      cut.push_back(k);
-      ws_cur = 0;
-    }
-    t.ws_off = ws_cur;
-    ws_cur += need;
-    ws_max = std::max(ws_max, ws_cur);
-  }
-  cut.push_back(n);
-  if (!b.src.alloc(src_size) || !b.dst.alloc(dst_size) || !b.ws.alloc(ws_max) ||
-      !b.desc.alloc(n) || !b.res.alloc(n) || !b.order.alloc(n)) {
-    (void)hipGetLastError();
-    set_error("LZMA2 encode batch: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
-  if (!hip_ok(hipMemcpy(b.src.p, src, src_size, hipMemcpyHostToDevice), "upload src") ||
-      (dst_init &&
-       !hip_ok(hipMemcpy(b.dst.p, dst_init, dst_size, hipMemcpyHostToDevice), "upload dst")) ||
-      !hip_ok(hipMemcpy(b.desc.p, d.data(), n * sizeof(d[0]), hipMemcpyHostToDevice),
-              "upload descs") ||
-      !hip_ok(hipMemcpy(b.order.p, order.data(), n * sizeof(order[0]), hipMemcpyHostToDevice),
-              "upload order"))
-    return SZ_ERROR_FAIL;
-  for (size_t c = 0; c + 1 < cut.size(); ++c) {
-    const size_t lo = cut[c], cnt = cut[c + 1] - lo;
-    if (cnt == 0) continue;
-    if (lzma2encgpu_launch(b.desc.p, b.order.p, uint32_t(lo), uint32_t(cnt), uint32_t(n), b.src.p,
-                           b.dst.p, b.ws.p, b.res.p, kLzmaEncLanesDefault, nullptr) != 0) {
-      set_error("LZMA2 encode batch kernel launch failed");
-      return SZ_ERROR_FAIL;
-    }
-  }
-  return SZ_OK;
+  static const char what[] = "LZMA2 encode batch";
+  const SRes r = b.lay_out(
+      what, descs, n, src_size, dst_size, workspace_limit,
+      [](const LzmaEncGpuStreamDesc& d) { return d.dst_cap; },
+      [](const LzmaEncGpuStreamDesc& d) { return d.src_len; }, lzma2enc_slice_bytes);
+  if (r != SZ_OK) return r;
+  return b.queue(what, in_caller_order(descs, b.plan), true, src, src_size, dst_init, dst_size,
+                 [&](uint32_t lo, uint32_t cnt) {
+                   return lzma2encgpu_launch(b.desc.p, b.order.p, lo, cnt, uint32_t(n), b.src.p,
+                                             b.dst.p, b.ws.p, b.res.p, kLzmaEncLanesDefault,
+                                             nullptr);
+                 });
 }
 
 // Lzma2Enc_SetProps' and LzmaEnc_SetProps' verdict on the props, the
@@ -279,11 +212,8 @@ SRes encode_stream(const Byte* src, size_t src_len, size_t block_size, const lze
   DevArr<uint64_t> g_off;
   DevArr<LzmaEncGpuResult> g_total;
   const uint64_t out_cap = slots_bytes + 1;
-  if (!g_out.alloc(size_t(out_cap)) || !g_off.alloc(n + 1) || !g_total.alloc(1)) {
-    (void)hipGetLastError();
-    set_error("LZMA2 encode: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  const SRes ar = alloc_all("LZMA2 encode", g_out, size_t(out_cap), g_off, n + 1, g_total, 1);
+  if (ar != SZ_OK) return ar;
   if (lzma2encgpu_launch_compact(s.b.desc.p, s.b.res.p, uint32_t(n), s.b.dst.p, g_out.p, out_cap,
                                  g_off.p, g_total.p, nullptr) != 0) {
     set_error("LZMA2 compaction kernel launch failed");
@@ -325,8 +255,7 @@ void put_varint(std::vector<uint8_t>& out, uint64_t v) {
 }
 
 // the block checks of an xz stream, on the device over the uploaded source
-SRes block_checks(const Stream& s, unsigned check_type, unsigned check_size,
-                  std::vector<uint8_t>& checks) {
+SRes block_checks(const Stream& s, unsigned check_size, std::vector<uint8_t>& checks) {
   const size_t n = s.descs.size();
   checks.assign(n * check_size, 0);
   if (check_size == 0 || n == 0) return SZ_OK;
@@ -335,47 +264,11 @@ SRes block_checks(const Stream& s, unsigned check_type, unsigned check_size,
     off[i] = s.descs[i].src_off;
     len[i] = s.descs[i].src_len;
   }
-  DevArr<uint64_t> g_off, g_len;
-  DevArr<uint8_t> g_val;
-  if (!g_off.alloc(n) || !g_len.alloc(n) || !g_val.alloc(n * 32)) {
-    (void)hipGetLastError();
-    return SZ_ERROR_MEM;
-  }
-  if (!hip_ok(hipMemcpy(g_off.p, off.data(), n * 8, hipMemcpyHostToDevice), "upload offsets") ||
-      !hip_ok(hipMemcpy(g_len.p, len.data(), n * 8, hipMemcpyHostToDevice), "upload lengths"))
-    return SZ_ERROR_FAIL;
-  SRes r;
-  if (check_type == LZMA_GPU_XZ_CHECK_SHA256) {
-    r = Sha256Gpu_Batch(s.b.src.p, g_off.p, g_len.p, n, LZMA_GPU_SHA256_AUTO, g_val.p, nullptr);
-  } else {
-    const size_t n_chunks = CrcGpu_PlanChunks(len.data(), n, nullptr, nullptr);
-    if (n_chunks == size_t(-1)) return SZ_ERROR_UNSUPPORTED;
-    std::vector<uint32_t> base(n), range(n_chunks ? n_chunks : 1);
-    CrcGpu_PlanChunks(len.data(), n, base.data(), range.data());
-    DevArr<uint32_t> g_base, g_range;
-    DevArr<uint64_t> g_chunk;
-    if (!g_base.alloc(n) || !g_range.alloc(n_chunks) || !g_chunk.alloc(n_chunks)) {
-      (void)hipGetLastError();
-      return SZ_ERROR_MEM;
-    }
-    if (!hip_ok(hipMemcpy(g_base.p, base.data(), n * 4, hipMemcpyHostToDevice), "upload plan") ||
-        !hip_ok(hipMemcpy(g_range.p, range.data(), n_chunks * 4, hipMemcpyHostToDevice),
-                "upload plan"))
-      return SZ_ERROR_FAIL;
-    if (check_type == LZMA_GPU_XZ_CHECK_CRC32)
-      r = CrcGpu_Batch(s.b.src.p, g_off.p, g_len.p, n, g_base.p, g_range.p, n_chunks, 0xFFFFFFFFu,
-                       0xFFFFFFFFu, reinterpret_cast<uint32_t*>(g_chunk.p),
-                       reinterpret_cast<uint32_t*>(g_val.p), nullptr);
-    else
-      r = Crc64Gpu_Batch(s.b.src.p, g_off.p, g_len.p, n, g_base.p, g_range.p, n_chunks,
-                         ~uint64_t(0), ~uint64_t(0), g_chunk.p,
-                         reinterpret_cast<uint64_t*>(g_val.p), nullptr);
-    if (r == SZ_OK && !hip_ok(hipDeviceSynchronize(), "xz block checks")) r = SZ_ERROR_FAIL;
-  }
-  if (r != SZ_OK) return r;
+  RangeChecks k;
+  SRes r = k.prepare("xz encode", check_size, off, len);
+  if (r != SZ_OK || (r = k.launch(s.b.src.p)) != SZ_OK) return r;
   if (!hip_ok(hipDeviceSynchronize(), "xz block checks") ||
-      !hip_ok(hipMemcpy(checks.data(), g_val.p, n * check_size, hipMemcpyDeviceToHost),
-              "download checks"))
+      !k.fetch(checks.data(), "download checks"))
     return SZ_ERROR_FAIL;
   return SZ_OK;
 }
@@ -403,7 +296,7 @@ SRes xz_encode(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
   if (srcLen != 0) {
     const SRes er = encode_stream(src, srcLen, norm.blockSize, q, s);
     if (er != SZ_OK) return er;
-    const SRes kr = block_checks(s, check_type, check_size, checks);
+    const SRes kr = block_checks(s, check_size, checks);
     if (kr != SZ_OK) return kr;
   }
   const size_t n = s.descs.size();
@@ -527,16 +420,6 @@ SRes lzma2enc_encode(Handle* h, ISeqOutStream* outStream, ISeqInStream* inStream
   return SZ_OK;
 }
 
-template <class F>
-SRes guarded(const char* what, F f) {
-  try {
-    return f();
-  } catch (const std::exception&) {
-    set_error(what);
-    return SZ_ERROR_MEM;
-  }
-}
-
 }  // namespace
 
 extern "C" SRes Lzma2EncGpu_EncodeBatchHost(const LzmaEncGpuStreamDesc* descs, size_t n,
@@ -547,14 +430,9 @@ extern "C" SRes Lzma2EncGpu_EncodeBatchHost(const LzmaEncGpuStreamDesc* descs, s
     if (!ensure_device()) return SZ_ERROR_FAIL;
     if (n == 0) return SZ_OK;
     Batch b;
-    const SRes r = run_batch(descs, n, src, src_size, dst, dst_size, workspace_limit, b);
-    if (r != SZ_OK) return r;
-    if (!hip_ok(hipDeviceSynchronize(), "LZMA2 encode batch") ||
-        !hip_ok(hipMemcpy(results, b.res.p, n * sizeof(results[0]), hipMemcpyDeviceToHost),
-                "download results") ||
-        !hip_ok(hipMemcpy(dst, b.dst.p, dst_size, hipMemcpyDeviceToHost), "download dst"))
-      return SZ_ERROR_FAIL;
-    return SZ_OK;
+    SRes r = run_batch(descs, n, src, src_size, dst, dst_size, workspace_limit, b);
+    if (r != SZ_OK || (r = b.wait("LZMA2 encode batch", results, n)) != SZ_OK) return r;
+    return b.download_dst(dst, 0, dst_size) ? SZ_OK : SZ_ERROR_FAIL;
   });
 }
 

@@ -15,6 +15,14 @@ __host__ __device__ inline int32_t lzma2enc_check(const LzmaEncGpuStreamDesc& d)
   if (r != lzenc::kOk) return r;
   return (d.ws_off & 15u) ? lzenc::kErrParam : lzenc::kOk;
 }
+// a block's workspace slice in bytes, wherever it is put; 0 for a descriptor
+// the kernel refuses with its own per-block code
+inline uint64_t lzma2enc_slice_bytes(const LzmaEncGpuStreamDesc& d) {
+  LzmaEncGpuStreamDesc t = d;
+  t.ws_off = 0;
+  if (lzma2enc_check(t) != lzenc::kOk) return 0;
+  return lzenc::lzma2enc_layout(lzmaenc_params(t), t.src_len).bytes;
+}
 
 // Two launches on `stream` over blocks order[first, first + count) of the n
 // descriptors (order null: index order): the grid clears every block's hash

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "crc32_device.h"
+#include "host_batch.h"
 #include "lzma_device.h"
 #include "lzma_gpu_internal.h"
 
@@ -525,12 +526,8 @@ static SRes plan_batch(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order, Lzma
 // C ABI: no exception crosses it (host allocation failure -> SZ_ERROR_MEM).
 static SRes plan_batch_nothrow(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order,
                                LzmaGpuPlan* plan, const LzmaGpuPlanOptions& o) {
-  try {
-    return plan_batch(descs, n, order, plan, o);
-  } catch (const std::exception&) {
-    set_error("plan: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  return lzgpu_host::guarded("plan: host allocation failed",
+                             [&]() { return plan_batch(descs, n, order, plan, o); });
 }
 
 SRes LzmaGpu_PlanBatchEx(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order,
@@ -714,58 +711,35 @@ static SRes decode_batch_host(const LzmaGpuStreamDesc* descs, size_t n, const By
     if (pr != SZ_OK) return pr;
   }
   if (plan_out) *plan_out = plan;
-  const size_t ws = size_t(plan.workspace_bytes);
-  void *d_src = nullptr, *d_dst = nullptr, *d_ws = nullptr, *d_desc = nullptr, *d_order = nullptr,
-       *d_res = nullptr;
-  SRes r = SZ_ERROR_MEM;
-  do {
-    if (!hip_ok(hipMalloc(&d_src, std::max<size_t>(src_bytes, 16)), "alloc src")) break;
-    if (!hip_ok(hipMalloc(&d_dst, std::max<size_t>(dst_bytes, 16)), "alloc dst")) break;
-    if (!hip_ok(hipMalloc(&d_ws, std::max<size_t>(ws, 16)), "alloc workspace")) break;
-    if (!hip_ok(hipMalloc(&d_desc, n * sizeof(LzmaGpuStreamDesc)), "alloc desc")) break;
-    if (!hip_ok(hipMalloc(&d_order, n * sizeof(uint32_t)), "alloc order")) break;
-    if (!hip_ok(hipMalloc(&d_res, n * sizeof(LzmaGpuResult)), "alloc results")) break;
-    r = SZ_ERROR_FAIL;
-    if (src_bytes && !hip_ok(hipMemcpy(d_src, src, src_bytes, hipMemcpyHostToDevice), "H2D src"))
-      break;
-    if (!hip_ok(hipMemcpy(d_desc, d.data(), n * sizeof(LzmaGpuStreamDesc), hipMemcpyHostToDevice),
-                "H2D desc"))
-      break;
-    if (!hip_ok(hipMemcpy(d_order, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice),
-                "H2D order"))
-      break;
-    if (LzmaGpu_DecodeBatchEx(&plan, static_cast<LzmaGpuStreamDesc*>(d_desc),
-                              static_cast<uint32_t*>(d_order), static_cast<Byte*>(d_src),
-                              static_cast<Byte*>(d_dst), d_ws, static_cast<LzmaGpuResult*>(d_res),
-                              nullptr) != SZ_OK)
-      break;
-    if (!hip_ok(hipDeviceSynchronize(), "decode kernel")) break;
-    if (!hip_ok(hipMemcpy(results, d_res, n * sizeof(LzmaGpuResult), hipMemcpyDeviceToHost),
-                "D2H results"))
-      break;
-    if (dst_bytes && !hip_ok(hipMemcpy(dst, d_dst, dst_bytes, hipMemcpyDeviceToHost), "D2H dst"))
-      break;
-    r = SZ_OK;
-  } while (0);
-  (void)hipFree(d_src);
-  (void)hipFree(d_dst);
-  (void)hipFree(d_ws);
-  (void)hipFree(d_desc);
-  (void)hipFree(d_order);
-  (void)hipFree(d_res);
-  return r;
+  lzgpu_host::DevArr<Byte> d_src, d_dst, d_ws;
+  lzgpu_host::DevArr<LzmaGpuStreamDesc> d_desc;
+  lzgpu_host::DevArr<uint32_t> d_order;
+  lzgpu_host::DevArr<LzmaGpuResult> d_res;
+  SRes r = lzgpu_host::alloc_all("batch", d_src, src_bytes, d_dst, dst_bytes, d_ws,
+                                 size_t(plan.workspace_bytes), d_res, n);
+  if (r != SZ_OK) return r;
+  if (src_bytes && !hip_ok(hipMemcpy(d_src.p, src, src_bytes, hipMemcpyHostToDevice), "H2D src"))
+    return SZ_ERROR_FAIL;
+  if ((r = lzgpu_host::upload(d_desc, d, "batch")) != SZ_OK ||
+      (r = lzgpu_host::upload(d_order, order, "batch")) != SZ_OK)
+    return r;
+  if (LzmaGpu_DecodeBatchEx(&plan, d_desc.p, d_order.p, d_src.p, d_dst.p, d_ws.p, d_res.p,
+                            nullptr) != SZ_OK ||
+      !hip_ok(hipDeviceSynchronize(), "decode kernel") ||
+      !hip_ok(hipMemcpy(results, d_res.p, n * sizeof(LzmaGpuResult), hipMemcpyDeviceToHost),
+              "D2H results") ||
+      (dst_bytes && !hip_ok(hipMemcpy(dst, d_dst.p, dst_bytes, hipMemcpyDeviceToHost), "D2H dst")))
+    return SZ_ERROR_FAIL;
+  return SZ_OK;
 }
 
 SRes LzmaGpu_DecodeBatchHostOpt(const LzmaGpuStreamDesc* descs, size_t n, const Byte* src,
                                 size_t src_bytes, Byte* dst, size_t dst_bytes,
                                 LzmaGpuResult* results, const LzmaGpuPlanOptions* opt,
                                 LzmaGpuPlan* plan_out) {
-  try {
+  return lzgpu_host::guarded("batch: host allocation failed", [&]() {
     return decode_batch_host(descs, n, src, src_bytes, dst, dst_bytes, results, opt, plan_out);
-  } catch (const std::exception&) {
-    set_error("batch: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  });
 }
 
 SRes LzmaGpu_DecodeBatchHost(const LzmaGpuStreamDesc* descs, size_t n, const Byte* src,

@@ -5,12 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <exception>
-#include <numeric>
 #include <string.h>
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
+#include "host_batch.h"
 #include "lzma_gpu_internal.h"
 #include "lzmaenc_device.h"
 #include "lzmaenc_internal.h"
@@ -68,41 +67,20 @@ extern "C" SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps* props, int writeEn
   return SZ_OK;
 }
 
-static uint64_t slice_bytes(const LzmaEncGpuStreamDesc& d) {
-  LzmaEncGpuStreamDesc t = d;
-  t.ws_off = 0;
-  if (lzmaenc_check(t) != lzenc::kOk) return 0;
-  return lzenc::lzmaenc_layout(lzmaenc_params(t), t.src_len).bytes;
-}
-
-static void longest_first(const LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order) {
-  std::iota(order, order + n, 0u);
-  std::stable_sort(order, order + n,
-                   [&](uint32_t a, uint32_t b) { return descs[a].src_len > descs[b].src_len; });
-}
-
-static SRes plan_batch(LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order,
-                       uint64_t* workspace_bytes) {
-  if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  uint64_t at = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t need = slice_bytes(descs[i]);
-    descs[i].ws_off = need ? at : 0;
-    at += need;
-  }
-  if (workspace_bytes) *workspace_bytes = at;
-  if (order) longest_first(descs, n, order);
-  return SZ_OK;
-}
-
 extern "C" SRes LzmaEncGpu_PlanBatch(LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order,
                                      uint64_t* workspace_bytes) {
-  try {
-    return plan_batch(descs, n, order, workspace_bytes);
-  } catch (const std::exception&) {
-    set_error("LZMA encode plan: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
+  return guarded("LZMA encode plan: host allocation failed", [&]() -> SRes {
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t need = lzmaenc_slice_bytes(descs[i]);
+      descs[i].ws_off = need ? at : 0;
+      at += need;
+    }
+    if (workspace_bytes) *workspace_bytes = at;
+    if (order) longest_first(n, [&](uint32_t i) { return descs[i].src_len; }, order);
+    return SZ_OK;
+  });
 }
 
 extern "C" SRes LzmaEncGpu_EncodeBatch(const LzmaEncGpuStreamDesc* d_descs, const uint32_t* d_order,
@@ -127,96 +105,35 @@ extern "C" SRes LzmaEncGpu_EncodeBatch(const LzmaEncGpuStreamDesc* d_descs, cons
 static SRes encode_batch_host(const LzmaEncGpuStreamDesc* descs, size_t n, const Byte* src,
                               size_t src_size, Byte* dst, size_t dst_size,
                               LzmaEncGpuResult* results, uint64_t workspace_limit, bool one_item) {
+  static const char what[] = "LZMA encode batch";
   if (!ensure_device()) return SZ_ERROR_FAIL;
   if (n == 0) return SZ_OK;
-  if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  for (size_t i = 0; i < n; ++i) {
-    const LzmaEncGpuStreamDesc& d = descs[i];
-    if (d.src_off > src_size || d.src_len > src_size - d.src_off || d.dst_off > dst_size ||
-        d.dst_cap > dst_size - d.dst_off)
-      return SZ_ERROR_PARAM;
-  }
-  if (workspace_limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if (!hip_ok(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo")) return SZ_ERROR_FAIL;
-    workspace_limit = free_b / 2;
-  }
-  // longest first: the waves of a launch start in index order
-  std::vector<uint32_t> order(n);
-  longest_first(descs, n, order.data());
-  // launches: consecutive streams of the order while their slices fit the limit
-  std::vector<LzmaEncGpuStreamDesc> d(n);
-  std::vector<size_t> cut{0};
-  uint64_t ws_max = 0, ws_cur = 0;
-  for (size_t k = 0; k < n; ++k) {
-    d[k] = descs[order[k]];
-    const uint64_t need = slice_bytes(d[k]);
-    if (need > workspace_limit) {
-      set_error("LZMA encode batch: one stream's workspace slice exceeds the limit");
-      return SZ_ERROR_MEM;
-    }
-    if (ws_cur + need > workspace_limit) {
-      cut.push_back(k);
-      ws_cur = 0;
-    }
-    d[k].ws_off = ws_cur;
-    ws_cur += need;
-    ws_max = std::max(ws_max, ws_cur);
-  }
-  cut.push_back(n);
-
-  DevArr<uint8_t> g_src, g_dst, g_ws;
-  DevArr<LzmaEncGpuStreamDesc> g_desc;
-  DevArr<LzmaEncGpuResult> g_res;
-  if (!g_src.alloc(src_size) || !g_dst.alloc(dst_size) || !g_ws.alloc(ws_max) ||
-      !g_desc.alloc(n) || !g_res.alloc(n)) {
-    (void)hipGetLastError();
-    set_error("LZMA encode batch: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
-  if (!hip_ok(hipMemcpy(g_src.p, src, src_size, hipMemcpyHostToDevice), "upload src") ||
-      (!one_item &&
-       !hip_ok(hipMemcpy(g_dst.p, dst, dst_size, hipMemcpyHostToDevice), "upload dst")) ||
-      !hip_ok(hipMemcpy(g_desc.p, d.data(), n * sizeof(d[0]), hipMemcpyHostToDevice),
-              "upload descs"))
-    return SZ_ERROR_FAIL;
-  for (size_t c = 0; c + 1 < cut.size(); ++c) {
-    const size_t lo = cut[c], cnt = cut[c + 1] - lo;
-    if (cnt == 0) continue;
-    if (lzmaencgpu_launch(g_desc.p + lo, nullptr, uint32_t(cnt), g_src.p, g_dst.p, g_ws.p,
-                          g_res.p + lo, kLzmaEncLanesDefault, nullptr) != 0) {
-      set_error("LZMA encode batch kernel launch failed");
-      return SZ_ERROR_FAIL;
-    }
-  }
-  std::vector<LzmaEncGpuResult> r(n);
-  if (!hip_ok(hipDeviceSynchronize(), "LZMA encode batch") ||
-      !hip_ok(hipMemcpy(r.data(), g_res.p, n * sizeof(r[0]), hipMemcpyDeviceToHost),
-              "download results"))
-    return SZ_ERROR_FAIL;
-  if (one_item) {
-    const uint64_t len = std::min<uint64_t>(r[0].dest_len, d[0].dst_cap);
-    if (len && !hip_ok(hipMemcpy(dst + d[0].dst_off, g_dst.p + d[0].dst_off, len,
-                                 hipMemcpyDeviceToHost), "download dst"))
-      return SZ_ERROR_FAIL;
-  } else if (!hip_ok(hipMemcpy(dst, g_dst.p, dst_size, hipMemcpyDeviceToHost), "download dst")) {
-    return SZ_ERROR_FAIL;
-  }
-  for (size_t k = 0; k < n; ++k) results[order[k]] = r[k];
-  return SZ_OK;
+  HostBatch<LzmaEncGpuStreamDesc, LzmaEncGpuResult> b;
+  SRes r = b.lay_out(
+      what, descs, n, src_size, dst_size, workspace_limit,
+      [](const LzmaEncGpuStreamDesc& d) { return d.dst_cap; },
+      [](const LzmaEncGpuStreamDesc& d) { return d.src_len; }, lzmaenc_slice_bytes);
+  if (r != SZ_OK) return r;
+  r = b.queue(what, in_launch_order(descs, b.plan), false, src, src_size,
+              one_item ? nullptr : dst, dst_size, [&](uint32_t lo, uint32_t cnt) {
+                return lzmaencgpu_launch(b.desc.p + lo, nullptr, cnt, b.src.p, b.dst.p, b.ws.p,
+                                         b.res.p + lo, kLzmaEncLanesDefault, nullptr);
+              });
+  if (r != SZ_OK || (r = b.wait_scattered(what, results)) != SZ_OK) return r;
+  const size_t off = one_item ? size_t(descs[0].dst_off) : 0;
+  const size_t len =
+      one_item ? size_t(std::min<uint64_t>(results[0].dest_len, descs[0].dst_cap)) : dst_size;
+  return b.download_dst(dst, off, len) ? SZ_OK : SZ_ERROR_FAIL;
 }
 
 extern "C" SRes LzmaEncGpu_EncodeBatchHost(const LzmaEncGpuStreamDesc* descs, size_t n,
                                            const Byte* src, size_t src_size, Byte* dst,
                                            size_t dst_size, LzmaEncGpuResult* results,
                                            uint64_t workspace_limit) {
-  try {
+  return guarded("LZMA encode batch: host allocation failed", [&]() {
     return encode_batch_host(descs, n, src, src_size, dst, dst_size, results, workspace_limit,
                              false);
-  } catch (const std::exception&) {
-    set_error("LZMA encode batch: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  });
 }
 
 extern "C" SRes LzmaEncode(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
@@ -258,13 +175,9 @@ extern "C" SRes LzmaEncode(Byte* dest, SizeT* destLen, const Byte* src, SizeT sr
   LzmaEncGpuResult r;
   r.res = SZ_ERROR_FAIL;
   r.dest_len = 0;
-  SRes res;
-  try {
-    res = encode_batch_host(&d, 1, src, srcLen, dest, *destLen, &r, 0, true);
-  } catch (const std::exception&) {
-    set_error("LZMA encode: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  const SRes res = guarded("LZMA encode: host allocation failed", [&]() {
+    return encode_batch_host(&d, 1, src, srcLen, dest, *destLen, &r, 0, true);
+  });
   if (res != SZ_OK) return res;
   *destLen = SizeT(r.dest_len);
   return r.res;

@@ -34,6 +34,14 @@ __host__ __device__ inline int32_t lzmaenc_check(const LzmaEncGpuStreamDesc& d) 
   if (r != lzenc::kOk) return r;
   return (d.ws_off & 15u) ? lzenc::kErrParam : lzenc::kOk;
 }
+// a stream's workspace slice in bytes, wherever it is put; 0 for a descriptor
+// the kernel refuses with its own per-stream code
+inline uint64_t lzmaenc_slice_bytes(const LzmaEncGpuStreamDesc& d) {
+  LzmaEncGpuStreamDesc t = d;
+  t.ws_off = 0;
+  if (lzmaenc_check(t) != lzenc::kOk) return 0;
+  return lzenc::lzmaenc_layout(lzmaenc_params(t), t.src_len).bytes;
+}
 
 // The first of the two launches alone (lzmaenc_bench.py times it separately).
 extern "C" int lzmaencgpu_launch_init(const LzmaEncGpuStreamDesc* d_descs, uint32_t n,

@@ -1,12 +1,10 @@
 // ppmd7_capi.hip -- C ABI of the PPMd7 batch decoder and encoder (include/lzma_gpu.h).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <exception>
-#include <numeric>
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
+#include "host_batch.h"
 #include "lzma_gpu_internal.h"
 #include "ppmd7_internal.h"
 
@@ -55,101 +53,38 @@ template <class Desc, class Res, class DstBytes, class Work, class Launch>
 static SRes batch_host(const Desc* descs, size_t n, const Byte* src, size_t src_size, Byte* dst,
                        size_t dst_size, Res* results, uint64_t workspace_limit,
                        DstBytes dst_bytes, Work work, Launch launch) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n == 0) return SZ_OK;
-  if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  for (size_t i = 0; i < n; ++i) {
-    const Desc& d = descs[i];
-    if (d.src_off > src_size || d.src_len > src_size - d.src_off || d.dst_off > dst_size ||
-        dst_bytes(d) > dst_size - d.dst_off)
-      return SZ_ERROR_PARAM;
-  }
-  if (workspace_limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if (!hip_ok(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo")) return SZ_ERROR_FAIL;
-    workspace_limit = free_b / 2;
-  }
-  // longest first: the workgroups of a launch start in index order
-  std::vector<uint32_t> order(n);
-  std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(),
-                   [&](uint32_t a, uint32_t b) { return work(descs[a]) > work(descs[b]); });
-  // launches: consecutive streams of the order while their slices fit the limit
-  std::vector<Desc> d(n);
-  std::vector<size_t> cut{0};
-  uint64_t ws_max = 0, ws_cur = 0;
-  for (size_t k = 0; k < n; ++k) {
-    d[k] = descs[order[k]];
-    const uint64_t need = props_ok(d[k].order, d[k].mem_size) ? ppmd7_slice_bytes(d[k].mem_size) : 0;
-    if (need > workspace_limit) {
-      set_error("PPMd7 batch: one stream's workspace slice exceeds the limit");
-      return SZ_ERROR_MEM;
-    }
-    if (ws_cur + need > workspace_limit) {
-      cut.push_back(k);
-      ws_cur = 0;
-    }
-    d[k].ws_off = ws_cur;
-    ws_cur += need;
-    ws_max = std::max(ws_max, ws_cur);
-  }
-  cut.push_back(n);
-
-  DevArr<uint8_t> g_src, g_dst, g_ws;
-  DevArr<Desc> g_desc;
-  DevArr<Res> g_res;
-  if (!g_src.alloc(src_size) || !g_dst.alloc(dst_size) || !g_ws.alloc(ws_max) ||
-      !g_desc.alloc(n) || !g_res.alloc(n)) {
-    (void)hipGetLastError();
-    set_error("PPMd7 batch: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
-  if (!hip_ok(hipMemcpy(g_src.p, src, src_size, hipMemcpyHostToDevice), "upload src") ||
-      !hip_ok(hipMemcpy(g_dst.p, dst, dst_size, hipMemcpyHostToDevice), "upload dst") ||
-      !hip_ok(hipMemcpy(g_desc.p, d.data(), n * sizeof(d[0]), hipMemcpyHostToDevice),
-              "upload descs"))
-    return SZ_ERROR_FAIL;
-  for (size_t c = 0; c + 1 < cut.size(); ++c) {
-    const size_t lo = cut[c], cnt = cut[c + 1] - lo;
-    if (cnt == 0) continue;
-    if (launch(g_desc.p + lo, uint32_t(cnt), g_src.p, g_dst.p, g_ws.p, g_res.p + lo, nullptr) != 0) {
-      set_error("PPMd7 batch kernel launch failed");
-      return SZ_ERROR_FAIL;
-    }
-  }
-  std::vector<Res> r(n);
-  if (!hip_ok(hipDeviceSynchronize(), "PPMd7 batch") ||
-      !hip_ok(hipMemcpy(r.data(), g_res.p, n * sizeof(r[0]), hipMemcpyDeviceToHost),
-              "download results") ||
-      !hip_ok(hipMemcpy(dst, g_dst.p, dst_size, hipMemcpyDeviceToHost), "download dst"))
-    return SZ_ERROR_FAIL;
-  for (size_t k = 0; k < n; ++k) results[order[k]] = r[k];
-  return SZ_OK;
+  static const char what[] = "PPMd7 batch";
+  return guarded("PPMd7 batch: host allocation failed", [&]() -> SRes {
+    if (!ensure_device()) return SZ_ERROR_FAIL;
+    if (n == 0) return SZ_OK;
+    HostBatch<Desc, Res> b;
+    SRes r = b.lay_out(what, descs, n, src_size, dst_size, workspace_limit, dst_bytes, work,
+                       [](const Desc& d) -> uint64_t {
+                         return props_ok(d.order, d.mem_size) ? ppmd7_slice_bytes(d.mem_size) : 0;
+                       });
+    if (r != SZ_OK) return r;
+    r = b.queue(what, in_launch_order(descs, b.plan), false, src, src_size, dst, dst_size,
+                [&](uint32_t lo, uint32_t cnt) {
+                  return launch(b.desc.p + lo, cnt, b.src.p, b.dst.p, b.ws.p, b.res.p + lo, nullptr);
+                });
+    if (r != SZ_OK || (r = b.wait_scattered(what, results)) != SZ_OK) return r;
+    return b.download_dst(dst, 0, dst_size) ? SZ_OK : SZ_ERROR_FAIL;
+  });
 }
 
 extern "C" SRes Ppmd7Gpu_DecodeBatchHost(const Ppmd7GpuStreamDesc* descs, size_t n, const Byte* src,
                                          size_t src_size, Byte* dst, size_t dst_size,
                                          Ppmd7GpuResult* results, uint64_t workspace_limit) {
-  try {
-    const auto len = [](const Ppmd7GpuStreamDesc& d) { return d.dst_len; };
-    return batch_host(descs, n, src, src_size, dst, dst_size, results, workspace_limit, len, len,
-                      ppmd7gpu_launch);
-  } catch (const std::exception&) {
-    set_error("PPMd7 batch: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  const auto len = [](const Ppmd7GpuStreamDesc& d) { return d.dst_len; };
+  return batch_host(descs, n, src, src_size, dst, dst_size, results, workspace_limit, len, len,
+                    ppmd7gpu_launch);
 }
 
 extern "C" SRes Ppmd7Gpu_EncodeBatchHost(const Ppmd7GpuEncDesc* descs, size_t n, const Byte* src,
                                          size_t src_size, Byte* dst, size_t dst_size,
                                          Ppmd7GpuEncResult* results, uint64_t workspace_limit) {
-  try {
-    return batch_host(
-        descs, n, src, src_size, dst, dst_size, results, workspace_limit,
-        [](const Ppmd7GpuEncDesc& d) { return d.dst_cap; },
-        [](const Ppmd7GpuEncDesc& d) { return d.src_len; }, ppmd7encgpu_launch);
-  } catch (const std::exception&) {
-    set_error("PPMd7 batch: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  return batch_host(
+      descs, n, src, src_size, dst, dst_size, results, workspace_limit,
+      [](const Ppmd7GpuEncDesc& d) { return d.dst_cap; },
+      [](const Ppmd7GpuEncDesc& d) { return d.src_len; }, ppmd7encgpu_launch);
 }

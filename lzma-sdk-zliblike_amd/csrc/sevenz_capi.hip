@@ -27,14 +27,11 @@
 #include <new>
 #include <vector>
 
+#include "host_batch.h"
 #include "lzma_gpu_internal.h"
 #include "ppmd7_internal.h"
 
-using lzgpu_host::crc32_host;
-using lzgpu_host::DevArr;
-using lzgpu_host::ensure_device;
-using lzgpu_host::hip_ok;
-using lzgpu_host::set_error;
+using namespace lzgpu_host;
 
 namespace {
 
@@ -802,17 +799,14 @@ struct PpmdBatch {
     if (stream) (void)hipStreamDestroy(stream);
   }
   SRes start(std::vector<Unit*>& us, const Byte* d_arc, Byte* dst) {
+    std::vector<Unit*> found;
     for (Unit* u : us)
-      if (u->method == kPpmd) which.push_back(u);
-    const size_t n = which.size();
+      if (u->method == kPpmd) found.push_back(u);
+    const size_t n = found.size();
     if (n == 0) return SZ_OK;
-    // longest first: the launch starts its workgroups in index order
-    std::stable_sort(which.begin(), which.end(),
-                     [](const Unit* a, const Unit* b) { return a->unpack > b->unpack; });
     std::vector<Ppmd7GpuStreamDesc> descs(n);
-    uint64_t ws = 0;
     for (size_t k = 0; k < n; ++k) {
-      const Unit& u = *which[k];
+      const Unit& u = *found[k];
       Ppmd7GpuStreamDesc& d = descs[k];
       d.src_off = u.pack_off;
       d.src_len = u.avail;
@@ -820,18 +814,18 @@ struct PpmdBatch {
       d.dst_len = u.unpack;
       d.order = u.props[0];
       d.mem_size = u.props[1] | (u.props[2] << 8) | (u.props[3] << 16) | (uint32_t(u.props[4]) << 24);
-      d.ws_off = ws;
-      ws += ppmd7_slice_bytes(d.mem_size);
     }
-    if (!d_ws.alloc(ws) || !d_desc.alloc(n) || !d_res.alloc(n)) {
-      (void)hipGetLastError();
-      set_error("7z: device allocation failed (PPMd workspace)");
-      return SZ_ERROR_MEM;
-    }
-    if (!hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "7z PPMd stream") ||
-        !hip_ok(hipMemcpy(d_desc.p, descs.data(), n * sizeof(descs[0]), hipMemcpyHostToDevice),
-                "7z H2D"))
+    // one launch, longest first (no limit: the plan cannot fail)
+    LaunchPlan p;
+    launch_plan(n, [&](uint32_t i) { return descs[i].dst_len; },
+                [&](uint32_t i) { return ppmd7_slice_bytes(descs[i].mem_size); }, ~uint64_t(0), p);
+    descs = in_launch_order(descs.data(), p);
+    for (size_t k = 0; k < n; ++k) which.push_back(found[p.order[k]]);
+    SRes r = alloc_all("7z", d_ws, size_t(p.ws_max), d_res, n);
+    if (r != SZ_OK) return r;
+    if (!hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "7z PPMd stream"))
       return SZ_ERROR_FAIL;
+    if ((r = upload(d_desc, descs, "7z")) != SZ_OK) return r;
     if (!ppmd7gpu_launch ||
         ppmd7gpu_launch(d_desc.p, uint32_t(n), d_arc, dst, d_ws.p, d_res.p, stream) != 0) {
       set_error("7z: PPMd7 batch kernel launch failed");
@@ -843,8 +837,7 @@ struct PpmdBatch {
     const size_t n = which.size();
     if (n == 0) return SZ_OK;
     std::vector<Ppmd7GpuResult> res(n);
-    if (!hip_ok(hipStreamSynchronize(stream), "7z PPMd decode") ||
-        !hip_ok(hipMemcpy(res.data(), d_res.p, n * sizeof(res[0]), hipMemcpyDeviceToHost), "7z D2H"))
+    if (!hip_ok(hipStreamSynchronize(stream), "7z PPMd decode") || !download(res, d_res.p, "7z D2H"))
       return SZ_ERROR_FAIL;
     for (size_t k = 0; k < n; ++k) {
       const Unit& u = *which[k];
@@ -901,21 +894,12 @@ static SRes decode_units(std::vector<Unit*>& us, const Byte* d_arc, Byte* dst) {
   DevArr<LzmaGpuStreamDesc> d_desc;
   DevArr<uint32_t> d_order;
   DevArr<LzmaGpuResult> d_res;
-  if (!d_ws.alloc(plan.workspace_bytes) || !d_desc.alloc(n) || !d_order.alloc(n) ||
-      !d_res.alloc(n)) {
-    set_error("7z: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
-  if (!hip_ok(hipMemcpy(d_desc.p, descs.data(), n * sizeof(LzmaGpuStreamDesc),
-                        hipMemcpyHostToDevice), "7z H2D") ||
-      !hip_ok(hipMemcpy(d_order.p, order.data(), n * 4, hipMemcpyHostToDevice), "7z H2D"))
-    return SZ_ERROR_FAIL;
-  if ((r = LzmaGpu_DecodeBatchEx(&plan, d_desc.p, d_order.p, d_arc, dst, d_ws.p, d_res.p,
+  if ((r = alloc_all("7z", d_ws, size_t(plan.workspace_bytes), d_res, n)) != SZ_OK ||
+      (r = upload(d_desc, descs, "7z")) != SZ_OK || (r = upload(d_order, order, "7z")) != SZ_OK ||
+      (r = LzmaGpu_DecodeBatchEx(&plan, d_desc.p, d_order.p, d_arc, dst, d_ws.p, d_res.p,
                                  nullptr)) != SZ_OK)
     return r;
-  if (!hip_ok(hipDeviceSynchronize(), "7z decode") ||
-      !hip_ok(hipMemcpy(res.data(), d_res.p, n * sizeof(LzmaGpuResult), hipMemcpyDeviceToHost),
-              "7z D2H"))
+  if (!hip_ok(hipDeviceSynchronize(), "7z decode") || !download(res, d_res.p, "7z D2H"))
     return SZ_ERROR_FAIL;
   for (size_t k = 0; k < n; ++k) which[k]->res = accept(*which[k], res[k]);
   return SZ_OK;
@@ -1006,49 +990,20 @@ SRes run_jobs(std::vector<Job>& jobs, const Byte* d_arc, Byte* d_dst, uint64_t d
     DevArr<Bcj2GpuJob> d_jobs;
     DevArr<int32_t> d_res;
     std::vector<int32_t> res(n);
-    if (!d_jobs.alloc(n) || !d_res.alloc(n)) return SZ_ERROR_MEM;
-    if (!hip_ok(hipMemcpy(d_jobs.p, b2.data(), n * sizeof(Bcj2GpuJob), hipMemcpyHostToDevice),
-                "7z H2D"))
-      return SZ_ERROR_FAIL;
+    RINOK7(upload(d_jobs, b2, "7z"));
+    RINOK7(alloc_all("7z", d_res, n));
     RINOK7(Bcj2Gpu_Batch(d_jobs.p, n, d_res.p, nullptr));
-    if (!hip_ok(hipDeviceSynchronize(), "7z BCJ2") ||
-        !hip_ok(hipMemcpy(res.data(), d_res.p, n * 4, hipMemcpyDeviceToHost), "7z D2H"))
+    if (!hip_ok(hipDeviceSynchronize(), "7z BCJ2") || !download(res, d_res.p, "7z D2H"))
       return SZ_ERROR_FAIL;
     for (size_t k = 0; k < n; ++k) b2_job[k]->res = res[k];
   }
-  const size_t nb = bcj_off.size();
-  if (nb) {  // x86_Convert(outBuffer, outSize, 0, &state0, 0) per BCJ folder
-    DevArr<uint64_t> d64;
-    DevArr<uint32_t> d32;
-    std::vector<uint64_t> h64(bcj_off);
-    h64.insert(h64.end(), bcj_len.begin(), bcj_len.end());
-    h64.resize(3 * nb, 0);
-    std::vector<uint32_t> h32(2 * nb, 0);
-    if (!d64.alloc(3 * nb) || !d32.alloc(2 * nb)) return SZ_ERROR_MEM;
-    if (!hip_ok(hipMemcpy(d64.p, h64.data(), h64.size() * 8, hipMemcpyHostToDevice), "7z H2D") ||
-        !hip_ok(hipMemcpy(d32.p, h32.data(), h32.size() * 4, hipMemcpyHostToDevice), "7z H2D"))
-      return SZ_ERROR_FAIL;
-    SRes r = BcjGpu_X86Batch(d_dst, d64.p, d64.p + nb, d32.p, d32.p + nb, d64.p + 2 * nb, nb, 0,
-                             nullptr);
-    if (r != SZ_OK) return r;
-    if (!hip_ok(hipDeviceSynchronize(), "7z BCJ")) return SZ_ERROR_FAIL;
-  } else if (!hip_ok(hipDeviceSynchronize(), "7z copy")) {
-    return SZ_ERROR_FAIL;
-  }
-  if (const size_t na = arm_off.size()) {  // ARM_Convert(outBuffer, outSize, 0, 0) per ARM folder
-    DevArr<uint64_t> d64;  // off, len, done
-    DevArr<uint32_t> d32;  // ip = 0
-    std::vector<uint64_t> h64(arm_off);
-    h64.insert(h64.end(), arm_len.begin(), arm_len.end());
-    h64.resize(3 * na, 0);
-    if (!d64.alloc(3 * na) || !d32.alloc(na)) return SZ_ERROR_MEM;
-    if (!hip_ok(hipMemcpy(d64.p, h64.data(), h64.size() * 8, hipMemcpyHostToDevice), "7z H2D") ||
-        !hip_ok(hipMemset(d32.p, 0, na * 4), "7z memset"))
-      return SZ_ERROR_FAIL;
-    SRes r = BraGpu_Batch(7, d_dst, d64.p, d64.p + na, d32.p, d64.p + 2 * na, na, 0, nullptr);
-    if (r != SZ_OK) return r;
-    if (!hip_ok(hipDeviceSynchronize(), "7z ARM")) return SZ_ERROR_FAIL;
-  }
+  // x86_Convert(outBuffer, outSize, 0, &state0, 0) per BCJ folder, then
+  // ARM_Convert(outBuffer, outSize, 0, 0) per ARM folder
+  FilterJob x86, arm;
+  RINOK7(queue_filter("7z", x86, 4, d_dst, bcj_off, bcj_len, nullptr, 0));
+  if (!hip_ok(hipDeviceSynchronize(), "7z BCJ")) return SZ_ERROR_FAIL;
+  RINOK7(queue_filter("7z", arm, 7, d_dst, arm_off, arm_len, nullptr, 0));
+  if (!arm_off.empty() && !hip_ok(hipDeviceSynchronize(), "7z ARM")) return SZ_ERROR_FAIL;
   return SZ_OK;
 }
 
@@ -1098,9 +1053,8 @@ SRes open_archive(const Byte* arc, size_t size, Archive& x) {
     const uint64_t nbytes = one ? jobs[0].units[0].avail : uint64_t(size);
     if (one) jobs[0].units[0].pack_off = 0;
     DevArr<Byte> d_arc, d_out;
-    if (!d_arc.alloc(size_t(nbytes)) ||
-        !d_out.alloc(unpacked.size() + size_t(bcj2_temp_bytes(jobs))))
-      return SZ_ERROR_MEM;
+    RINOK7(alloc_all("7z", d_arc, size_t(nbytes), d_out,
+                     unpacked.size() + size_t(bcj2_temp_bytes(jobs))));
     if (nbytes && !hip_ok(hipMemcpy(d_arc.p, arc + at, size_t(nbytes), hipMemcpyHostToDevice),
                           "7z H2D"))
       return SZ_ERROR_FAIL;
@@ -1232,10 +1186,7 @@ static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t s
   if (nf) {
     if (!ensure_device()) return SZ_ERROR_FAIL;
     DevArr<Byte> d_arc, d_dst;
-    if (!d_arc.alloc(size) || !d_dst.alloc(total + bcj2_temp_bytes(jobs))) {
-      set_error("7z: device allocation failed");
-      return SZ_ERROR_MEM;
-    }
+    RINOK7(alloc_all("7z", d_arc, size, d_dst, size_t(total + bcj2_temp_bytes(jobs))));
     if (!hip_ok(hipMemcpy(d_arc.p, archive, size, hipMemcpyHostToDevice), "7z H2D"))
       return SZ_ERROR_FAIL;
     RINOK7(run_jobs(jobs, d_arc.p, d_dst.p, total));
@@ -1258,28 +1209,11 @@ static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t s
     }
     const size_t nc = off.size();
     std::vector<uint32_t> crc(nc);
-    if (nc) {
-      const size_t nch = CrcGpu_PlanChunks(len.data(), nc, nullptr, nullptr);
-      if (nch == size_t(-1)) return SZ_ERROR_PARAM;
-      std::vector<uint32_t> cb(nc + nch);
-      CrcGpu_PlanChunks(len.data(), nc, cb.data(), cb.data() + nc);
-      std::vector<uint64_t> ol(off);
-      ol.insert(ol.end(), len.begin(), len.end());
-      DevArr<uint64_t> d_ol;
-      DevArr<uint32_t> d_cb, d_chunk, d_crc;
-      if (!d_ol.alloc(2 * nc) || !d_cb.alloc(cb.size()) || !d_chunk.alloc(nch) ||
-          !d_crc.alloc(nc))
-        return SZ_ERROR_MEM;
-      if (!hip_ok(hipMemcpy(d_ol.p, ol.data(), ol.size() * 8, hipMemcpyHostToDevice), "7z H2D") ||
-          !hip_ok(hipMemcpy(d_cb.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice), "7z H2D"))
-        return SZ_ERROR_FAIL;
-      if ((r = CrcGpu_Batch(d_dst.p, d_ol.p, d_ol.p + nc, nc, d_cb.p, d_cb.p + nc, nch,
-                            0xFFFFFFFFu, 0xFFFFFFFFu, d_chunk.p, d_crc.p, nullptr)) != SZ_OK)
-        return r;
-      if (!hip_ok(hipDeviceSynchronize(), "7z CRC") ||
-          !hip_ok(hipMemcpy(crc.data(), d_crc.p, nc * 4, hipMemcpyDeviceToHost), "7z D2H"))
-        return SZ_ERROR_FAIL;
-    }
+    RangeChecks checks;
+    RINOK7(checks.prepare("7z", 4, off, len));
+    RINOK7(checks.launch(d_dst.p));
+    if (nc && (!hip_ok(hipDeviceSynchronize(), "7z CRC") || !checks.fetch(crc.data(), "7z D2H")))
+      return SZ_ERROR_FAIL;
     for (size_t k = 0; k < nc; ++k)
       if (tag[k] >= 0 && crc[k] != a.folders[size_t(tag[k])].crc) jobs[size_t(tag[k])].res = SZ_ERROR_CRC;
     for (size_t i = 0; i < nfiles; ++i) {
@@ -1316,24 +1250,18 @@ SRes LzmaGpu_7zOpenEx(const Byte* archive, size_t size, LzmaGpu7zFolder* folders
                       size_t* n_files, UInt16* names, size_t names_cap, size_t* names_len,
                       UInt64* unpack_total, unsigned flags) {
   if (flags & ~LZMA_GPU_7Z_KNOWN_FLAGS) return SZ_ERROR_PARAM;
-  try {
+  return guarded("7z: host allocation failed", [&]() {
     return sz_open(archive, size, folders, folder_cap, n_folders, files, file_cap, n_files, names,
                    names_cap, names_len, unpack_total, flags);
-  } catch (const std::exception&) {
-    set_error("7z: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  });
 }
 
 SRes LzmaGpu_7zExtractEx(Byte* dest, SizeT* destLen, const Byte* archive, size_t size,
                          SRes* file_res, size_t file_cap, unsigned flags) {
   if (flags & ~LZMA_GPU_7Z_KNOWN_FLAGS) return SZ_ERROR_PARAM;
-  try {
+  return guarded("7z: host allocation failed", [&]() {
     return sz_extract(dest, destLen, archive, size, file_res, file_cap, flags);
-  } catch (const std::exception&) {
-    set_error("7z: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  });
 }
 
 SRes LzmaGpu_7zOpen(const Byte* archive, size_t size, LzmaGpu7zFolder* folders, size_t folder_cap,

@@ -6,12 +6,12 @@
 
 #include <algorithm>
 #include <chrono>
-#include <exception>
 #include <numeric>
 #include <string.h>
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
+#include "host_batch.h"
 #include "lzma2enc_internal.h"
 #include "lzma_gpu_internal.h"
 #include "lzmaenc_internal.h"
@@ -385,73 +385,29 @@ void write_sig(Byte* sig32, const Bytes& hdr, uint64_t pack_area_size) {
 
 // ---------------------------------------------------------------- the device pipeline
 
-template <class T>
-bool upload(DevArr<T>& g, const std::vector<T>& h, const char* what) {
-  if (!g.alloc(h.size())) {
-    (void)hipGetLastError();
-    set_error("7z write: device allocation failed");
-    return false;
-  }
-  return h.empty() ||
-         hip_ok(hipMemcpy(g.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), what);
-}
-
-// The streams of one kind of one round, longest first, with workspace offsets
-// that restart at every cut: launches [cut[c], cut[c + 1]).
+// The streams of one kind of one round in launch order (longest first), with
+// workspace offsets that restart at every cut of the plan.
 template <class Desc>
 struct KindBatch {
-  std::vector<Desc> d;           // sorted
-  std::vector<uint32_t> piece;   // d[k]'s piece
-  std::vector<size_t> cut;
-  uint64_t ws_max = 0;
+  std::vector<Desc> d;
+  std::vector<uint32_t> piece;  // d[k]'s piece
+  LaunchPlan plan;
 };
 
 template <class Desc, class Slice>
 SRes lay_out(KindBatch<Desc>& b, uint64_t limit, Slice slice) {
-  const size_t n = b.d.size();
-  std::vector<uint32_t> order(n);
-  std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(),
-                   [&](uint32_t x, uint32_t y) { return b.d[x].src_len > b.d[y].src_len; });
-  std::vector<Desc> d(n);
-  std::vector<uint32_t> piece(n);
-  b.cut.assign(1, 0);
-  b.ws_max = 0;
-  uint64_t cur = 0;
-  for (size_t k = 0; k < n; ++k) {
-    d[k] = b.d[order[k]];
-    piece[k] = b.piece[order[k]];
-    const uint64_t need = slice(d[k]);
-    if (need > limit) {
-      set_error("7z write: one stream's workspace slice exceeds the limit");
-      return SZ_ERROR_MEM;
-    }
-    if (cur + need > limit) {
-      b.cut.push_back(k);
-      cur = 0;
-    }
-    d[k].ws_off = cur;
-    cur += need;
-    b.ws_max = std::max(b.ws_max, cur);
+  if (!launch_plan(b.d.size(), [&](uint32_t i) { return b.d[i].src_len; },
+                   [&](uint32_t i) { return slice(b.d[i]); }, limit, b.plan)) {
+    set_error("7z write: one stream's workspace slice exceeds the limit");
+    return SZ_ERROR_MEM;
   }
-  b.cut.push_back(n);
-  b.d.swap(d);
+  b.d = in_launch_order(b.d.data(), b.plan);
+  std::vector<uint32_t> piece(b.piece.size());
+  for (size_t k = 0; k < piece.size(); ++k) piece[k] = b.piece[b.plan.order[k]];
   b.piece.swap(piece);
   return SZ_OK;
 }
 
-uint64_t lzma_slice(const LzmaEncGpuStreamDesc& d) {
-  LzmaEncGpuStreamDesc t = d;
-  t.ws_off = 0;
-  if (lzmaenc_check(t) != lzenc::kOk) return 0;
-  return lzenc::lzmaenc_layout(lzmaenc_params(t), t.src_len).bytes;
-}
-uint64_t lzma2_slice(const LzmaEncGpuStreamDesc& d) {
-  LzmaEncGpuStreamDesc t = d;
-  t.ws_off = 0;
-  if (lzma2enc_check(t) != lzenc::kOk) return 0;
-  return lzenc::lzma2enc_layout(lzmaenc_params(t), t.src_len).bytes;
-}
 uint64_t ppmd_slice(const Ppmd7GpuEncDesc& d) { return ppmd7_slice_bytes(d.mem_size); }
 
 struct Device {
@@ -462,95 +418,58 @@ struct Device {
   uint64_t ws_bytes = 0;
 };
 
-// queues the launches of one kind's batch; results land at res + k for d[k]
+// uploads one kind's descriptors and queues its launches; results land at
+// res + k for d[k]
+template <class Desc, class Launch>
+SRes launch_kind(const char* what, const KindBatch<Desc>& b, DevArr<Desc>& g, uint64_t* launches,
+                 Launch launch) {
+  if (b.d.empty()) return SZ_OK;
+  const SRes r = upload(g, b.d, "7z write");
+  if (r != SZ_OK) return r;
+  return queue_launches(what, b.plan, [&](uint32_t lo, uint32_t cnt) {
+    ++*launches;
+    return launch(lo, cnt);
+  });
+}
 SRes launch_lzma(const KindBatch<LzmaEncGpuStreamDesc>& b, DevArr<LzmaEncGpuStreamDesc>& g,
                  const uint8_t* src, uint8_t* dst, uint8_t* ws, LzmaEncGpuResult* res,
                  uint64_t* launches) {
-  if (b.d.empty()) return SZ_OK;
-  if (!upload(g, b.d, "upload descs")) return SZ_ERROR_FAIL;
-  for (size_t c = 0; c + 1 < b.cut.size(); ++c) {
-    const size_t lo = b.cut[c], cnt = b.cut[c + 1] - lo;
-    if (cnt == 0) continue;
-    if (lzmaencgpu_launch(g.p + lo, nullptr, uint32_t(cnt), src, dst, ws, res + lo,
-                          kLzmaEncLanesDefault, nullptr) != 0) {
-      set_error("7z write: LZMA encode launch failed");
-      return SZ_ERROR_FAIL;
-    }
-    ++*launches;
-  }
-  return SZ_OK;
+  return launch_kind("7z write: LZMA encode", b, g, launches, [&](uint32_t lo, uint32_t cnt) {
+    return lzmaencgpu_launch(g.p + lo, nullptr, cnt, src, dst, ws, res + lo, kLzmaEncLanesDefault,
+                             nullptr);
+  });
 }
 SRes launch_lzma2(const KindBatch<LzmaEncGpuStreamDesc>& b, DevArr<LzmaEncGpuStreamDesc>& g,
                   const uint8_t* src, uint8_t* dst, uint8_t* ws, LzmaEncGpuResult* res,
                   uint64_t* launches) {
-  if (b.d.empty()) return SZ_OK;
-  if (!upload(g, b.d, "upload descs")) return SZ_ERROR_FAIL;
-  for (size_t c = 0; c + 1 < b.cut.size(); ++c) {
-    const size_t lo = b.cut[c], cnt = b.cut[c + 1] - lo;
-    if (cnt == 0) continue;
-    if (lzma2encgpu_launch(g.p, nullptr, uint32_t(lo), uint32_t(cnt), uint32_t(b.d.size()), src,
-                           dst, ws, res, kLzmaEncLanesDefault, nullptr) != 0) {
-      set_error("7z write: LZMA2 encode launch failed");
-      return SZ_ERROR_FAIL;
-    }
-    ++*launches;
-  }
-  return SZ_OK;
+  return launch_kind("7z write: LZMA2 encode", b, g, launches, [&](uint32_t lo, uint32_t cnt) {
+    return lzma2encgpu_launch(g.p, nullptr, lo, cnt, uint32_t(b.d.size()), src, dst, ws, res,
+                              kLzmaEncLanesDefault, nullptr);
+  });
 }
 SRes launch_ppmd(const KindBatch<Ppmd7GpuEncDesc>& b, DevArr<Ppmd7GpuEncDesc>& g,
                  const uint8_t* src, uint8_t* dst, uint8_t* ws, Ppmd7GpuEncResult* res,
                  uint64_t* launches) {
-  if (b.d.empty()) return SZ_OK;
-  if (!upload(g, b.d, "upload descs")) return SZ_ERROR_FAIL;
-  for (size_t c = 0; c + 1 < b.cut.size(); ++c) {
-    const size_t lo = b.cut[c], cnt = b.cut[c + 1] - lo;
-    if (cnt == 0) continue;
-    if (ppmd7encgpu_launch(g.p + lo, uint32_t(cnt), src, dst, ws, res + lo, nullptr) != 0) {
-      set_error("7z write: PPMd7 encode launch failed");
-      return SZ_ERROR_FAIL;
-    }
-    ++*launches;
-  }
-  return SZ_OK;
+  return launch_kind("7z write: PPMd7 encode", b, g, launches, [&](uint32_t lo, uint32_t cnt) {
+    return ppmd7encgpu_launch(g.p + lo, cnt, src, dst, ws, res + lo, nullptr);
+  });
 }
 
 // CrcCalc of every data item over the uploaded source (queued, not awaited)
-struct CrcJob {
-  DevArr<uint64_t> off, len, chunk;
-  DevArr<uint32_t> base, range, crc;
-  size_t n = 0;
-};
-SRes queue_crcs(const LzmaGpu7zItem* items, size_t n, const uint8_t* d_src, CrcJob& j) {
+SRes queue_crcs(const LzmaGpu7zItem* items, size_t n, const uint8_t* d_src, RangeChecks& j) {
   std::vector<uint64_t> off, len;
   for (size_t i = 0; i < n; ++i)
     if (has_data(items[i])) {
       off.push_back(items[i].src_off);
       len.push_back(items[i].size);
     }
-  j.n = off.size();
-  if (j.n == 0) return SZ_OK;
-  const size_t n_chunks = CrcGpu_PlanChunks(len.data(), j.n, nullptr, nullptr);
-  if (n_chunks == size_t(-1)) return SZ_ERROR_UNSUPPORTED;
-  std::vector<uint32_t> base(j.n), range(n_chunks ? n_chunks : 1);
-  CrcGpu_PlanChunks(len.data(), j.n, base.data(), range.data());
-  range.resize(n_chunks);
-  if (!upload(j.off, off, "upload offsets") || !upload(j.len, len, "upload lengths") ||
-      !upload(j.base, base, "upload plan") || !upload(j.range, range, "upload plan"))
-    return SZ_ERROR_FAIL;
-  if (!j.chunk.alloc(n_chunks) || !j.crc.alloc(j.n)) {
-    (void)hipGetLastError();
-    return SZ_ERROR_MEM;
-  }
-  return CrcGpu_Batch(d_src, j.off.p, j.len.p, j.n, j.base.p, j.range.p, n_chunks, 0xFFFFFFFFu,
-                      0xFFFFFFFFu, reinterpret_cast<uint32_t*>(j.chunk.p), j.crc.p, nullptr);
+  const SRes r = j.prepare("7z write", 4, off, len);
+  return r == SZ_OK ? j.launch(d_src) : r;
 }
 
-// the x86 and ARM filters, encoding, in place over the filtered folders
-struct FilterJob {
-  DevArr<uint64_t> x64, a64;
-  DevArr<uint32_t> x32, a32;
-};
-SRes queue_filters(const Plan& p, uint8_t* d_src, FilterJob& j) {
+// the x86 and ARM filters, encoding, in place over the filtered folders:
+// x86_Convert(data, size, 0, &state0, 1) and ARM_Convert(data, size, 0, 1) per folder
+SRes queue_filters(const Plan& p, uint8_t* d_src, FilterJob& x86, FilterJob& arm) {
   std::vector<uint64_t> xo, xl, ao, al;
   for (const FolderPlan& f : p.folders) {
     const uint32_t filter = p.methods[f.method].filter;
@@ -562,29 +481,8 @@ SRes queue_filters(const Plan& p, uint8_t* d_src, FilterJob& j) {
       al.push_back(f.size);
     }
   }
-  if (const size_t nx = xo.size()) {  // x86_Convert(data, size, 0, &state0, 1) per folder
-    std::vector<uint64_t> h64(xo);
-    h64.insert(h64.end(), xl.begin(), xl.end());
-    h64.resize(3 * nx, 0);
-    std::vector<uint32_t> h32(2 * nx, 0);
-    if (!upload(j.x64, h64, "upload ranges") || !upload(j.x32, h32, "upload ranges"))
-      return SZ_ERROR_FAIL;
-    const SRes r = BcjGpu_X86Batch(d_src, j.x64.p, j.x64.p + nx, j.x32.p, j.x32.p + nx,
-                                   j.x64.p + 2 * nx, nx, 1, nullptr);
-    if (r != SZ_OK) return r;
-  }
-  if (const size_t na = ao.size()) {  // ARM_Convert(data, size, 0, 1) per folder
-    std::vector<uint64_t> h64(ao);
-    h64.insert(h64.end(), al.begin(), al.end());
-    h64.resize(3 * na, 0);
-    std::vector<uint32_t> h32(na, 0);
-    if (!upload(j.a64, h64, "upload ranges") || !upload(j.a32, h32, "upload ranges"))
-      return SZ_ERROR_FAIL;
-    const SRes r = BraGpu_Batch(kFilterArm, d_src, j.a64.p, j.a64.p + na, j.a32.p,
-                                j.a64.p + 2 * na, na, 1, nullptr);
-    if (r != SZ_OK) return r;
-  }
-  return SZ_OK;
+  const SRes r = queue_filter("7z write", x86, kFilterX86, d_src, xo, xl, nullptr, 1);
+  return r == SZ_OK ? queue_filter("7z write", arm, kFilterArm, d_src, ao, al, nullptr, 1) : r;
 }
 
 // a filtered folder is converted in place: its range may not meet another's
@@ -667,11 +565,7 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
     t_last = t;
   };
   uint64_t limit = options ? options->workspace_limit : 0;
-  if (limit == 0) {
-    size_t free_b = 0, total_b = 0;
-    if (!hip_ok(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo")) return SZ_ERROR_FAIL;
-    limit = free_b / 2;
-  }
+  if (!default_workspace_limit(limit)) return SZ_ERROR_FAIL;
 
   // pieces and first-round slots, in folder order
   const size_t nf = p.folders.size();
@@ -747,7 +641,7 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
     }
   }
   SRes r;
-  if ((r = lay_out(lz, limit, lzma_slice)) != SZ_OK || (r = lay_out(l2, limit, lzma2_slice)) != SZ_OK ||
+  if ((r = lay_out(lz, limit, lzmaenc_slice_bytes)) != SZ_OK || (r = lay_out(l2, limit, lzma2enc_slice_bytes)) != SZ_OK ||
       (r = lay_out(pp, limit, ppmd_slice)) != SZ_OK)
     return r;
   for (size_t k = 0; k < lz.d.size(); ++k) pieces[lz.piece[k]].slot = uint32_t(k);
@@ -755,24 +649,21 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   for (size_t k = 0; k < pp.d.size(); ++k) pieces[pp.piece[k]].slot = uint32_t(k);
 
   Device g;
-  g.ws_bytes = std::max(lz.ws_max, std::max(l2.ws_max, pp.ws_max));
+  g.ws_bytes = std::max(lz.plan.ws_max, std::max(l2.plan.ws_max, pp.plan.ws_max));
   const size_t lz_cap = lz.d.size() * (1 + kReencodeRounds);
   const size_t pp_cap = pp.d.size() * (1 + kReencodeRounds);
-  if (!g.src.alloc(src_size) || !g.slots.alloc(size_t(at)) || !g.ws.alloc(size_t(g.ws_bytes)) ||
-      !g.lz_res.alloc(lz_cap) || !g.l2_res.alloc(l2.d.size()) || !g.pp_res.alloc(pp_cap)) {
-    (void)hipGetLastError();
-    set_error("7z write: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  if ((r = alloc_all("7z write", g.src, src_size, g.slots, size_t(at), g.ws, size_t(g.ws_bytes),
+                     g.lz_res, lz_cap, g.l2_res, l2.d.size(), g.pp_res, pp_cap)) != SZ_OK)
+    return r;
   if (src_size && !hip_ok(hipMemcpy(g.src.p, src, src_size, hipMemcpyHostToDevice), "upload src"))
     return SZ_ERROR_FAIL;
   mark(LZMA_GPU_7Z_STAGE_UPLOAD);
   // everything below is queued on the null stream, in order
-  CrcJob crc;
-  FilterJob filt;
+  RangeChecks crc;
+  FilterJob filt_x86, filt_arm;
   if ((r = queue_crcs(items, n, g.src.p, crc)) != SZ_OK) return r;
   mark(LZMA_GPU_7Z_STAGE_CRC);
-  if ((r = queue_filters(p, g.src.p, filt)) != SZ_OK) return r;
+  if ((r = queue_filters(p, g.src.p, filt_x86, filt_arm)) != SZ_OK) return r;
   mark(LZMA_GPU_7Z_STAGE_FILTER);
   DevArr<LzmaEncGpuStreamDesc> g_lz, g_l2;
   DevArr<Ppmd7GpuEncDesc> g_pp;
@@ -831,14 +722,10 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
       return SZ_ERROR_FAIL;
     }
     // the workspace stands: cut by its size (every slice fitted it before)
-    if ((r = lay_out(lz_next, g.ws_bytes, lzma_slice)) != SZ_OK ||
+    if ((r = lay_out(lz_next, g.ws_bytes, lzmaenc_slice_bytes)) != SZ_OK ||
         (r = lay_out(pp_next, g.ws_bytes, ppmd_slice)) != SZ_OK)
       return r;
-    if (!g.retry[round - 1].alloc(size_t(need))) {
-      (void)hipGetLastError();
-      set_error("7z write: device allocation failed");
-      return SZ_ERROR_MEM;
-    }
+    if ((r = alloc_all("7z write", g.retry[round - 1], size_t(need))) != SZ_OK) return r;
     lz_at = lz_used;
     pp_at = pp_used;
     for (size_t k = 0; k < lz_next.d.size(); ++k) {
@@ -879,13 +766,10 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   DevArr<SzGpuPackPiece> g_pieces;
   DevArr<uint64_t> g_scratch, g_off, g_fsize;
   DevArr<LzmaEncGpuResult> g_total;
-  if (!upload(g_pieces, pieces, "upload pieces")) return SZ_ERROR_FAIL;
-  if (!g.out.alloc(size_t(out_cap)) || !g_scratch.alloc(SzGpu_PackScratch(np)) ||
-      !g_off.alloc(np) || !g_fsize.alloc(nf) || !g_total.alloc(1)) {
-    (void)hipGetLastError();
-    set_error("7z write: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  if ((r = upload(g_pieces, pieces, "7z write")) != SZ_OK ||
+      (r = alloc_all("7z write", g.out, size_t(out_cap), g_scratch, SzGpu_PackScratch(np), g_off,
+                     np, g_fsize, nf, g_total, 1)) != SZ_OK)
+    return r;
   SzGpuPackArgs a;
   memset(&a, 0, sizeof(a));
   a.d_pieces = g_pieces.p;
@@ -924,8 +808,7 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   }
   if ((nf && !hip_ok(hipMemcpy(fsize.data(), g_fsize.p, nf * 8, hipMemcpyDeviceToHost),
                      "download pack sizes")) ||
-      (crc.n && !hip_ok(hipMemcpy(crcs.data(), crc.crc.p, crc.n * 4, hipMemcpyDeviceToHost),
-                        "download CRCs")))
+      !crc.fetch(crcs.data(), "download CRCs"))
     return SZ_ERROR_FAIL;
 
   // header
@@ -984,23 +867,13 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   return SZ_OK;
 }
 
-template <class F>
-SRes guarded(F f) {
-  try {
-    return f();
-  } catch (const std::exception&) {
-    set_error("7z write: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
-}
-
 }  // namespace
 
 extern "C" SRes LzmaGpu_7zWritePlan(const LzmaGpu7zItem* items, size_t n, size_t src_size,
                                     size_t names_len, const LzmaGpu7zMethod* methods,
                                     size_t n_methods, LzmaGpu7zFolder* folders, size_t folder_cap,
                                     size_t* n_folders, size_t* n_pieces, uint64_t* dest_bound) {
-  return guarded([&]() -> SRes {
+  return guarded("7z write: host allocation failed", [&]() -> SRes {
     Plan p;
     const SRes r = make_plan(items, n, src_size, names_len, methods, n_methods, p);
     if (r != SZ_OK) return r;
@@ -1022,7 +895,7 @@ extern "C" SRes LzmaGpu_7zWriteHeader(const LzmaGpu7zFolder* folders, size_t n_f
                                       size_t names_len, unsigned flags, Byte* header,
                                       size_t header_cap, size_t* header_len, Byte* sig32,
                                       uint64_t pack_area_size) {
-  return guarded([&]() -> SRes {
+  return guarded("7z write: host allocation failed", [&]() -> SRes {
     if (flags & ~unsigned(LZMA_GPU_7Z_HEADER_STUB)) return SZ_ERROR_PARAM;
     Bytes o;
     const SRes r = (flags & LZMA_GPU_7Z_HEADER_STUB)
@@ -1041,7 +914,7 @@ extern "C" SRes LzmaGpu_7zWrite(Byte* dest, SizeT* destLen, const Byte* src, siz
                                 const LzmaGpu7zItem* items, size_t n, const UInt16* names,
                                 size_t names_len, const LzmaGpu7zMethod* methods, size_t n_methods,
                                 const LzmaGpu7zWriteOptions* options, LzmaGpu7zWriteStats* stats) {
-  return guarded([&]() {
+  return guarded("7z write: host allocation failed", [&]() {
     return write_archive(dest, destLen, src, src_size, items, n, names, names_len, methods,
                          n_methods, options, stats);
   });

@@ -17,18 +17,14 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <exception>
 #include <vector>
 
+#include "host_batch.h"
 #include "lzma_gpu_internal.h"
 
 static_assert(sizeof(LzmaGpuXzBlock) == 104, "LzmaGpuXzBlock layout (lzmagpu.py XzBlock)");
 
-using lzgpu_host::ensure_device;
-using lzgpu_host::hip_ok;
-using lzgpu_host::set_error;
-using lzgpu_host::crc32_host;
-using lzgpu_host::DevArr;
+using namespace lzgpu_host;
 
 namespace {
 
@@ -282,10 +278,7 @@ SizeT x86_Convert(Byte* data, SizeT size, UInt32 ip, UInt32* state, int encoding
   const uint32_t is[2] = {ip, *state};
   uint64_t done = 0;
   uint32_t st = 0;
-  if (!d.alloc(size) || !meta.alloc(3) || !m32.alloc(2)) {
-    set_error("x86_Convert: device allocation failed");
-    return 0;
-  }
+  if (alloc_all("x86_Convert", d, size, meta, 3, m32, 2) != SZ_OK) return 0;
   if (!hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), "x86_Convert H2D") ||
       !hip_ok(hipMemcpy(meta.p, ol, 16, hipMemcpyHostToDevice), "x86_Convert H2D") ||
       !hip_ok(hipMemcpy(m32.p, is, 8, hipMemcpyHostToDevice), "x86_Convert H2D"))
@@ -317,10 +310,7 @@ SizeT bra_convert_host(unsigned kind, const char* name, Byte* data, SizeT size, 
   DevArr<uint32_t> m32;   // ip
   const uint64_t ol[2] = {0, uint64_t(size)};
   uint64_t done = 0;
-  if (!d.alloc(size) || !meta.alloc(3) || !m32.alloc(1)) {
-    set_error("Bra converter: device allocation failed");
-    return 0;
-  }
+  if (alloc_all("Bra converter", d, size, meta, 3, m32, 1) != SZ_OK) return 0;
   if (!hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), name) ||
       !hip_ok(hipMemcpy(meta.p, ol, 16, hipMemcpyHostToDevice), name) ||
       !hip_ok(hipMemcpy(m32.p, &ip, 4, hipMemcpyHostToDevice), name))
@@ -344,10 +334,7 @@ void delta_host(Byte* state, unsigned delta, Byte* data, SizeT size, int encodin
   DevArr<uint64_t> meta;  // off, len
   DevArr<uint32_t> dl;
   const uint64_t ol[2] = {0, uint64_t(size)};
-  if (!d.alloc(size ? size : 1) || !st.alloc(256) || !meta.alloc(2) || !dl.alloc(1)) {
-    set_error("Delta: device allocation failed");
-    return;
-  }
+  if (alloc_all("Delta", d, size, st, 256, meta, 2, dl, 1) != SZ_OK) return;
   if ((size && !hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), "Delta H2D")) ||
       !hip_ok(hipMemcpy(st.p, state, delta, hipMemcpyHostToDevice), "Delta H2D") ||
       !hip_ok(hipMemcpy(meta.p, ol, 16, hipMemcpyHostToDevice), "Delta H2D") ||
@@ -437,10 +424,8 @@ static int bcj2_host(const Byte* buf0, SizeT size0, const Byte* buf1, SizeT size
   DevArr<Byte> d;
   DevArr<Bcj2GpuJob> dj;
   DevArr<int32_t> dr;
-  if (!d.alloc(size_t(total)) || !dj.alloc(1) || !dr.alloc(1)) {
-    set_error("Bcj2_Decode: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  const SRes ar = alloc_all("Bcj2_Decode", d, size_t(total), dj, 1, dr, 1);
+  if (ar != SZ_OK) return ar;
   auto up = [&](uint64_t at, const Byte* p, uint64_t n) {
     return n == 0 || hip_ok(hipMemcpy(d.p + at, p, size_t(n), hipMemcpyHostToDevice), "Bcj2 H2D");
   };
@@ -478,12 +463,9 @@ static int bcj2_host(const Byte* buf0, SizeT size0, const Byte* buf1, SizeT size
 
 int Bcj2_Decode(const Byte* buf0, SizeT size0, const Byte* buf1, SizeT size1, const Byte* buf2,
                 SizeT size2, const Byte* buf3, SizeT size3, Byte* outBuf, SizeT outSize) {
-  try {
+  return guarded("Bcj2_Decode: host allocation failed", [&]() {
     return bcj2_host(buf0, size0, buf1, size1, buf2, size2, buf3, size3, outBuf, outSize);
-  } catch (const std::exception&) {
-    set_error("Bcj2_Decode: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  });
 }
 
 UInt64 Crc64Calc(const void* data, size_t size) {
@@ -497,10 +479,7 @@ UInt64 Crc64Calc(const void* data, size_t size) {
   DevArr<uint64_t> ol, chunks;
   DevArr<uint32_t> m;
   const uint64_t olh[3] = {0, cap, 0};
-  if (!d.alloc(size) || !ol.alloc(3) || !chunks.alloc(nch) || !m.alloc(1 + nch)) {
-    set_error("Crc64Calc: device allocation failed");
-    return 0;
-  }
+  if (alloc_all("Crc64Calc", d, size, ol, 3, chunks, nch, m, 1 + nch) != SZ_OK) return 0;
   uint64_t out = 0;
   if (!hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), "CRC-64 H2D") ||
       !hip_ok(hipMemcpy(ol.p, olh, 24, hipMemcpyHostToDevice), "CRC-64 H2D") ||
@@ -667,62 +646,36 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
   std::vector<uint32_t> order(n);
   LzmaGpuPlan plan;
   if ((r = LzmaGpu_PlanBatchEx(descs.data(), n, order.data(), &plan)) != SZ_OK) return r;
-  // check ranges (after the filters): CRC-32, CRC-64 and SHA-256 blocks, chunk
-  // plans for the CRCs
-  std::vector<uint64_t> off32, len32, off64, len64, offsha, lensha;
-  std::vector<size_t> idx32, idx64, idxsha;
-  for (size_t i = 0; i < n; ++i) {
-    if (blk[i].check_type == LZMA_GPU_XZ_CHECK_CRC32) {
-      idx32.push_back(i);
-      off32.push_back(blk[i].dst_off);
-      len32.push_back(blk[i].unpack_size);
-    } else if (blk[i].check_type == LZMA_GPU_XZ_CHECK_CRC64) {
-      idx64.push_back(i);
-      off64.push_back(blk[i].dst_off);
-      len64.push_back(blk[i].unpack_size);
-    } else if (blk[i].check_type == LZMA_GPU_XZ_CHECK_SHA256) {
-      idxsha.push_back(i);
-      offsha.push_back(blk[i].dst_off);
-      lensha.push_back(blk[i].unpack_size);
-    }
-  }
-  const size_t nch32 = CrcGpu_PlanChunks(len32.data(), len32.size(), nullptr, nullptr);
-  const size_t nch64 = CrcGpu_PlanChunks(len64.data(), len64.size(), nullptr, nullptr);
-  if (nch32 == size_t(-1) || nch64 == size_t(-1)) return SZ_ERROR_PARAM;
-  std::vector<uint32_t> cb32(len32.size() + nch32), cb64(len64.size() + nch64);
-  CrcGpu_PlanChunks(len32.data(), len32.size(), cb32.data(), cb32.data() + len32.size());
-  CrcGpu_PlanChunks(len64.data(), len64.size(), cb64.data(), cb64.data() + len64.size());
-
+  // check ranges (after the filters): the CRC-32, the CRC-64 and the SHA-256 blocks
+  struct Kind {
+    unsigned type, bytes;
+    std::vector<size_t> idx;
+    std::vector<uint64_t> off, len;
+    RangeChecks checks;
+  } kinds[3] = {{LZMA_GPU_XZ_CHECK_CRC32, 4, {}, {}, {}, {}},
+                {LZMA_GPU_XZ_CHECK_CRC64, 8, {}, {}, {}, {}},
+                {LZMA_GPU_XZ_CHECK_SHA256, 32, {}, {}, {}, {}}};
+  for (size_t i = 0; i < n; ++i)
+    for (Kind& k : kinds)
+      if (blk[i].check_type == k.type) {
+        k.idx.push_back(i);
+        k.off.push_back(blk[i].dst_off);
+        k.len.push_back(blk[i].unpack_size);
+      }
   DevArr<Byte> d_src, d_dst, d_ws;
   DevArr<LzmaGpuStreamDesc> d_desc;
-  DevArr<uint32_t> d_order, d_cb32, d_cb64, d_crc32, d_chunk32;
+  DevArr<uint32_t> d_order;
   DevArr<LzmaGpuResult> d_res;
-  DevArr<uint64_t> d_ol32, d_ol64, d_chunk64, d_crc64, d_olsha;
-  DevArr<Byte> d_sha;
-  if (!d_src.alloc(size) || !d_dst.alloc(total) || !d_ws.alloc(plan.workspace_bytes) ||
-      !d_desc.alloc(n) || !d_order.alloc(n) || !d_res.alloc(n) ||
-      !d_ol32.alloc(2 * off32.size()) || !d_cb32.alloc(cb32.size()) ||
-      !d_chunk32.alloc(nch32) || !d_crc32.alloc(off32.size()) ||
-      !d_ol64.alloc(2 * off64.size()) || !d_cb64.alloc(cb64.size()) ||
-      !d_chunk64.alloc(nch64) || !d_crc64.alloc(off64.size()) ||
-      !d_olsha.alloc(2 * offsha.size()) || !d_sha.alloc(32 * offsha.size())) {
-    set_error("XzDecode: device allocation failed");
-    return SZ_ERROR_MEM;
-  }
-  auto h2d = [](void* d, const void* h, size_t bytes) {
-    return bytes == 0 || hip_ok(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice), "XzDecode H2D");
-  };
-  std::vector<uint64_t> ol32(off32), ol64(off64), olsha(offsha);
-  ol32.insert(ol32.end(), len32.begin(), len32.end());
-  ol64.insert(ol64.end(), len64.begin(), len64.end());
-  olsha.insert(olsha.end(), lensha.begin(), lensha.end());
-  if (!h2d(d_src.p, file, size) || !h2d(d_desc.p, descs.data(), n * sizeof(LzmaGpuStreamDesc)) ||
-      !h2d(d_order.p, order.data(), n * 4) || !h2d(d_ol32.p, ol32.data(), ol32.size() * 8) ||
-      !h2d(d_cb32.p, cb32.data(), cb32.size() * 4) ||
-      !h2d(d_ol64.p, ol64.data(), ol64.size() * 8) ||
-      !h2d(d_cb64.p, cb64.data(), cb64.size() * 4) ||
-      !h2d(d_olsha.p, olsha.data(), olsha.size() * 8))
+  if ((r = alloc_all("XzDecode", d_src, size, d_dst, size_t(total), d_ws,
+                     size_t(plan.workspace_bytes), d_res, n)) != SZ_OK)
+    return r;
+  if (!hip_ok(hipMemcpy(d_src.p, file, size, hipMemcpyHostToDevice), "XzDecode H2D"))
     return SZ_ERROR_FAIL;
+  if ((r = upload(d_desc, descs, "XzDecode")) != SZ_OK ||
+      (r = upload(d_order, order, "XzDecode")) != SZ_OK)
+    return r;
+  for (Kind& k : kinds)
+    if ((r = k.checks.prepare("XzDecode", k.bytes, k.off, k.len)) != SZ_OK) return r;
   if ((r = LzmaGpu_DecodeBatchEx(&plan, d_desc.p, d_order.p, d_src.p, d_dst.p, d_ws.p, d_res.p,
                                  nullptr)) != SZ_OK)
     return r;
@@ -731,7 +684,7 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
   for (uint32_t depth = 0; depth < 3; ++depth) {
     for (uint32_t kind = 3; kind <= 9; ++kind) {
       std::vector<uint64_t> fo, fl;
-      std::vector<uint32_t> fp;
+      std::vector<uint32_t> fp;  // start ip / delta distance
       for (size_t i = 0; i < n; ++i) {
         const uint32_t nf = blk[i].num_filters;
         if (nf > depth && blk[i].filter_id[nf - 1 - depth] == kind) {
@@ -740,57 +693,24 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
           fp.push_back(blk[i].filter_prop[nf - 1 - depth]);
         }
       }
-      const size_t nb = fo.size();
-      if (nb == 0) continue;
-      DevArr<uint64_t> d64;  // off, len, done
-      DevArr<uint32_t> d32;  // ip / distance, x86 state
-      DevArr<Byte> dstate;   // delta states
-      fo.insert(fo.end(), fl.begin(), fl.end());
-      fo.resize(3 * nb, 0);
-      fp.resize(2 * nb, 0);  // states start at 0 (x86_Convert_Init, Delta_Init)
-      if (!d64.alloc(3 * nb) || !d32.alloc(2 * nb) || !dstate.alloc(kind == 3 ? 256 * nb : 1)) {
-        set_error("XzDecode: device allocation failed");
-        return SZ_ERROR_MEM;
-      }
-      if (!h2d(d64.p, fo.data(), fo.size() * 8) || !h2d(d32.p, fp.data(), fp.size() * 4) ||
-          (kind == 3 && !hip_ok(hipMemset(dstate.p, 0, 256 * nb), "XzDecode memset")))
-        return SZ_ERROR_FAIL;
-      if (kind == 3)
-        r = DeltaGpu_Batch(d_dst.p, d64.p, d64.p + nb, d32.p, dstate.p, nb, 0, nullptr);
-      else if (kind == 4)
-        r = BcjGpu_X86Batch(d_dst.p, d64.p, d64.p + nb, d32.p, d32.p + nb, d64.p + 2 * nb, nb, 0,
-                            nullptr);
-      else
-        r = BraGpu_Batch(kind, d_dst.p, d64.p, d64.p + nb, d32.p, d64.p + 2 * nb, nb, 0, nullptr);
-      if (r != SZ_OK) return r;
+      if (fo.empty()) continue;
+      FilterJob job;
+      if ((r = queue_filter("XzDecode", job, kind, d_dst.p, fo, fl, fp.data(), 0)) != SZ_OK)
+        return r;
       if (!hip_ok(hipDeviceSynchronize(), "XzDecode filters")) return SZ_ERROR_FAIL;
     }
   }
-  const size_t n32 = off32.size(), n64 = off64.size(), nsha = offsha.size();
-  if (n32 && (r = CrcGpu_Batch(d_dst.p, d_ol32.p, d_ol32.p + n32, n32, d_cb32.p, d_cb32.p + n32,
-                               nch32, 0xFFFFFFFFu, 0xFFFFFFFFu, d_chunk32.p, d_crc32.p,
-                               nullptr)) != SZ_OK)
-    return r;
-  if (n64 && (r = Crc64Gpu_Batch(d_dst.p, d_ol64.p, d_ol64.p + n64, n64, d_cb64.p, d_cb64.p + n64,
-                                 nch64, ~0ull, ~0ull, d_chunk64.p, d_crc64.p, nullptr)) != SZ_OK)
-    return r;
-  if (nsha && (r = Sha256Gpu_Batch(d_dst.p, d_olsha.p, d_olsha.p + nsha, nsha,
-                                   LZMA_GPU_SHA256_AUTO, d_sha.p, nullptr)) != SZ_OK)
-    return r;
+  for (Kind& k : kinds)
+    if ((r = k.checks.launch(d_dst.p)) != SZ_OK) return r;
   std::vector<LzmaGpuResult> res(n);
-  std::vector<uint32_t> crc32(n32);
-  std::vector<uint64_t> crc64(n64);
-  std::vector<Byte> sha(32 * nsha);
-  if (!hip_ok(hipDeviceSynchronize(), "XzDecode kernels") ||
-      !hip_ok(hipMemcpy(res.data(), d_res.p, n * sizeof(LzmaGpuResult), hipMemcpyDeviceToHost),
-              "XzDecode D2H") ||
-      (n32 && !hip_ok(hipMemcpy(crc32.data(), d_crc32.p, n32 * 4, hipMemcpyDeviceToHost),
-                      "XzDecode D2H")) ||
-      (n64 && !hip_ok(hipMemcpy(crc64.data(), d_crc64.p, n64 * 8, hipMemcpyDeviceToHost),
-                      "XzDecode D2H")) ||
-      (nsha && !hip_ok(hipMemcpy(sha.data(), d_sha.p, 32 * nsha, hipMemcpyDeviceToHost),
-                       "XzDecode D2H")) ||
-      !hip_ok(hipMemcpy(dest, d_dst.p, total, hipMemcpyDeviceToHost), "XzDecode D2H"))
+  std::vector<Byte> value[3];
+  if (!hip_ok(hipDeviceSynchronize(), "XzDecode kernels") || !download(res, d_res.p, "XzDecode D2H"))
+    return SZ_ERROR_FAIL;
+  for (size_t t = 0; t < 3; ++t) {
+    value[t].resize(kinds[t].idx.size() * kinds[t].bytes);
+    if (!kinds[t].checks.fetch(value[t].data(), "XzDecode D2H")) return SZ_ERROR_FAIL;
+  }
+  if (!hip_ok(hipMemcpy(dest, d_dst.p, total, hipMemcpyDeviceToHost), "XzDecode D2H"))
     return SZ_ERROR_FAIL;
   for (size_t i = 0; i < n; ++i) {
     const LzmaGpuResult& q = res[i];
@@ -798,21 +718,13 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
         q.dest_len != blk[i].unpack_size || q.src_len != blk[i].pack_size)
       fail[i] = SZ_ERROR_DATA;
   }
-  for (size_t k = 0; k < n32; ++k) {
-    const size_t i = idx32[k];
-    if (fail[i] == SZ_OK && crc32[k] != le32(file + blk[i].check_off)) fail[i] = SZ_ERROR_CRC;
-  }
-  for (size_t k = 0; k < n64; ++k) {
-    const size_t i = idx64[k];
-    const uint64_t want = uint64_t(le32(file + blk[i].check_off)) |
-                          (uint64_t(le32(file + blk[i].check_off + 4)) << 32);
-    if (fail[i] == SZ_OK && crc64[k] != want) fail[i] = SZ_ERROR_CRC;
-  }
-  for (size_t k = 0; k < nsha; ++k) {
-    const size_t i = idxsha[k];
-    if (fail[i] == SZ_OK && memcmp(&sha[32 * k], file + blk[i].check_off, 32) != 0)
-      fail[i] = SZ_ERROR_CRC;
-  }
+  // the values are little-endian on the device as in the file
+  for (size_t t = 0; t < 3; ++t)
+    for (size_t k = 0; k < kinds[t].idx.size(); ++k) {
+      const size_t i = kinds[t].idx[k], nb = kinds[t].bytes;
+      if (fail[i] == SZ_OK && memcmp(&value[t][nb * k], file + blk[i].check_off, nb) != 0)
+        fail[i] = SZ_ERROR_CRC;
+    }
   for (size_t i = 0; i < n; ++i)
     if (fail[i] != SZ_OK) {
       if (bad_block) *bad_block = int64_t(i);
@@ -825,20 +737,12 @@ static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
 // C ABI: no exception crosses it (host allocation failure -> SZ_ERROR_MEM).
 SRes LzmaGpu_XzIndex(const Byte* file, size_t size, LzmaGpuXzBlock* blocks, size_t cap,
                      size_t* n_blocks, uint64_t* unpack_total) {
-  try {
-    return xz_index(file, size, blocks, cap, n_blocks, unpack_total);
-  } catch (const std::exception&) {
-    set_error("xz: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  return guarded("xz: host allocation failed",
+                 [&]() { return xz_index(file, size, blocks, cap, n_blocks, unpack_total); });
 }
 
 SRes LzmaGpu_XzDecode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,
                       int64_t* bad_block) {
-  try {
-    return xz_decode(dest, destLen, file, size, bad_block);
-  } catch (const std::exception&) {
-    set_error("xz: host allocation failed");
-    return SZ_ERROR_MEM;
-  }
+  return guarded("xz: host allocation failed",
+                 [&]() { return xz_decode(dest, destLen, file, size, bad_block); });
 }

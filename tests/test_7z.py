@@ -248,3 +248,37 @@ def test_gpu_7z_bcj2_folders_round_trip(L):
     r, out, fres = L.SzExtract(bytes(bad), total)
     failed = {i for i, x in enumerate(fres[:len(plain)]) if x != 0}
     assert failed <= {i for i, f in enumerate(files) if f.folder == 100}
+
+
+@pytest.mark.gpu
+def test_gpu_7z_folder_and_file_crcs_fail_independently(L):
+    """One CRC batch covers the folders with a CRC and every file range; each
+    value goes back to its folder or its file.  Folder 0: a wrong folder CRC (all
+    its files fail, their own CRCs are right); folder 1: no folder CRC, the
+    middle file's CRC wrong; folder 2: a right folder CRC and a wrong CRC of its
+    last file; folder 3: one file, known by the folder CRC alone."""
+    import sevenzwrite as W
+
+    def folder(i, sizes, wrong_file=None, **kw):
+        true = [(f"f{i}/{k}", native.gen("text", 9700 + 10 * i + k, n)) for k, n in enumerate(sizes)]
+        f = W.Folder(true, method=(W.M_LZMA, W.M_LZMA2)[i % 2], **kw)
+        if wrong_file is not None:  # the recorded CRC belongs to other bytes of that length
+            f.files = list(true)
+            f.files[wrong_file] = (true[wrong_file][0], bytes(b ^ 1 for b in true[wrong_file][1]))
+        return f, [d for _, d in true]
+
+    parts = [folder(0, (700, 1300), crc=True), folder(1, (900, 401, 77), wrong_file=1),
+             folder(2, (1500, 650), wrong_file=1, crc=True), folder(3, (333,), crc=True)]
+    folders, plain = [f for f, _ in parts], [d for _, ds in parts for d in ds]
+    folders[0].data = bytes(b ^ 1 for b in folders[0].data)   # the recorded folder CRC only
+    arc = W.archive(folders)
+    r, fo, files, _, total = L.sz_open(arc)
+    assert r == 0 and [f.crc_defined for f in fo] == [1, 0, 1, 1] and len(files) == 8
+    r, out, fres = L.SzExtract(arc, total)
+    assert r == 3 and fres[:8] == [3, 3, 0, 3, 0, 0, 3, 0]
+    assert [out[f.dst_off:f.dst_off + f.size] for f in files] == plain
+    # the same archive with every recorded CRC right
+    good = W.archive([W.Folder(list(zip((n for n, _ in f.files), ds)), method=f.method, crc=f.crc)
+                      for f, (_, ds) in zip(folders, parts)])
+    r, out, fres = L.SzExtract(good, total)
+    assert r == 0 and fres[:8] == [0] * 8 and len(good) == len(arc)

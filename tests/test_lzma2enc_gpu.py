@@ -234,6 +234,65 @@ def test_what_the_kernel_refuses_and_the_empty_batch(L):
     assert L.lib.Lzma2EncGpu_EncodeBatch(None, None, 1, None, None, None, None, 48, None) == C.PARAM
 
 
+def host_batch(L, cases, golden, limit):
+    """Lzma2EncGpu_EncodeBatchHost over the cases, each with its block bound for
+    room, a poison byte between the slots and around them."""
+    src, dst_off = bytearray(b"\x5a"), 3
+    descs = (L.EncStreamDesc * max(len(cases), 1))()
+    for i, c in enumerate(cases):
+        r, d, _ = desc_of(L, c)
+        assert r == 0
+        ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(d), ctypes.sizeof(d))
+        data = C.data_of(c)
+        descs[i].src_off, descs[i].src_len, descs[i].dst_off, descs[i].dst_cap = (
+            len(src), len(data), dst_off, C.block_bound(len(data)))
+        src += data
+        dst_off += descs[i].dst_cap + 1
+    t0 = time.monotonic()
+    r, res, out = L.lzma2_encode_batch_host(descs, len(cases), bytes(src),
+                                            bytes([POISON]) * (dst_off + 5), limit)
+    assert time.monotonic() - t0 < STEP_LIMIT_S
+    return r, [(q.res, q.dest_len) for q in list(res)[:len(cases)]], out, descs
+
+
+def test_host_call_splits_launches_by_the_workspace_limit(L, golden):
+    """The host call's launches take (first, count) over a device copy of the
+    longest-first order and write results at the caller's index.  30 blocks of at
+    most 6,000 bytes with dictionaries of 4 and 64 KiB from the committed records
+    (the 13 of level 1, then other fast levels: the list has no 30 of level 1),
+    once in one launch and once in three."""
+    small = [g["case"] for g in golden["cases"] if g["res"] == C.OK
+             and C.size_of(g["case"]) <= 6000 and g["case"]["dict"] in (4096, 1 << 16)]
+    cases = sorted(small, key=lambda c: c["level"] != 1)[:30]
+    assert len(cases) == 30 and sum(c["level"] == 1 for c in cases) == 13
+    assert len({C.size_of(c) for c in cases}) > 20 and sum(C.size_of(c) == 0 for c in cases) == 3
+    r, order, ws = L.enc2_plan(host_batch(L, cases, golden, 0)[3], len(cases))
+    assert r == 0 and order != sorted(order)
+    limit = ws // 3 + (1 << 20)             # three launches
+    assert 2 * limit < ws < 3 * limit
+    r1, res1, out1, descs = host_batch(L, cases, golden, 0)
+    r3, res3, out3, _ = host_batch(L, cases, golden, limit)
+    assert r1 == 0 and r3 == 0, L.last_error()
+    assert res1 == res3 == [(C.OK, want_of(c, golden)["len"] - 1) for c in cases]
+    assert out1 == out3
+    at = 0
+    for c, q, (_, dl) in zip(cases, descs, res1):
+        assert out1[at:q.dst_off] == bytes([POISON]) * (q.dst_off - at)
+        C.check_block((C.OK, dl, desc_of(L, c)[2], out1[q.dst_off:q.dst_off + dl]),
+                      want_of(c, golden), C.key(c))
+        at = q.dst_off + q.dst_cap          # a block may use all of its slot on the way
+    assert out1[at:] == bytes([POISON]) * (len(out1) - at)
+    # one block alone over the limit, a range outside the buffers, nothing to do
+    r, _, out, _ = host_batch(L, cases, golden, 1 << 16)
+    assert r == 2 and out == bytes([POISON]) * len(out)
+    assert host_batch(L, [], golden, 0)[0] == 0
+    assert host_batch(L, [], golden, limit)[0] == 0
+    d = (L.EncStreamDesc * 1)(raw_desc(L, src_len=10, dst_cap=10))
+    assert L.lzma2_encode_batch_host(d, 1, b"123456789", bytes(10))[0] == C.PARAM
+    d = (L.EncStreamDesc * 1)(raw_desc(L, src_len=9, dst_off=1, dst_cap=10))
+    assert L.lzma2_encode_batch_host(d, 1, b"123456789", bytes(10), limit)[0] == C.PARAM
+
+
 def test_multi_block_buffer(L, golden):
     """LzmaGpu_Lzma2EncodeHost: 300,000 bytes of text and 70,000 random at
     blockSize 100,000 is the reference's multi-threaded layout."""

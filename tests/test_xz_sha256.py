@@ -70,6 +70,31 @@ def test_gpu_xz_mixed_checks_across_streams(L):
 
 
 @pytest.mark.gpu
+def test_gpu_xz_interleaved_check_kinds_fail_at_their_own_block(L):
+    """Blocks of a few hundred bytes whose check kinds alternate (streams with
+    checks 4 / 1 / 10 / 0 / 1 / 10 / 4): the k-th value of a kind's batch belongs
+    to that kind's k-th block, not to block k.  One stored check corrupted at a
+    time, in the first and in the last block of each kind: SZ_ERROR_CRC at that
+    block, and every other block's check still holds."""
+    kinds = (4, 1, 10, 0, 1, 10, 4)
+    plain = [native.gen("text", 9400 + i, 200 + 97 * i) for i in range(len(kinds))]
+    files = b"".join(M.make_stream([(d, {})], chk) for d, chk in zip(plain, kinds))
+    r, blocks, total = L.xz_index(files)
+    assert r == 0 and [b.check_type for b in blocks] == list(kinds)
+    assert L.XzDecode(files, total) == (0, b"".join(plain), -1)
+    for i, b in enumerate(blocks):
+        for at in {0, b.check_size - 1} if b.check_size else ():
+            broken = bytearray(files)
+            broken[b.check_off + at] ^= 0x10
+            assert L.XzDecode(bytes(broken), total) == (SZ_ERROR_CRC, b"", i), (i, at)
+    # two kinds broken at once: the first block in file order is the one named
+    broken = bytearray(files)
+    broken[blocks[5].check_off + 7] ^= 1
+    broken[blocks[4].check_off + 3] ^= 1
+    assert L.XzDecode(bytes(broken), total)[::2] == (SZ_ERROR_CRC, 4)
+
+
+@pytest.mark.gpu
 def test_gpu_xz_sha256_after_x86_filter(L):
     """The digest is of the block's final bytes: it is taken after the BCJ filter."""
     datas = [x86_code(9300 + i, n) for i, n in enumerate((5000, 70001, 3))]
