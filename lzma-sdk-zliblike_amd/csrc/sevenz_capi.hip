@@ -531,7 +531,10 @@ SRes read_header(Archive& x, Sd& s) {
     x.db.data_pos += kStartHeader;
     RINOK7(rd_num(s, &t));
   }
-  if (t == kEnd) return SZ_OK;
+  // no kFilesInfo: folders and no files (7zIn.c:981-982 returns here with its
+  // Fill arrays unset and never walks them: no file, no extract); the folder
+  // tables the open and extract calls walk are filled all the same
+  if (t == kEnd) return fill(x);
   if (t != kFilesInfo) return SZ_ERROR_ARCHIVE;
   uint32_t nf;
   RINOK7(rd_num32(s, &nf));
@@ -1007,6 +1010,22 @@ SRes run_jobs(std::vector<Job>& jobs, const Byte* d_arc, Byte* d_dst, uint64_t d
   return SZ_OK;
 }
 
+// Folder outputs tile one device buffer, BCJ2 temp streams behind them
+// (sz_extract, the packed-header decode below): every size a folder states
+// goes into one running sum, and a sum that wraps or reaches 2^63 ends the
+// open with SZ_ERROR_MEM -- what SzArEx_Extract returns when a folder's size
+// cannot be allocated (7zIn.c:1354-1369).  7z numbers are full 64-bit, so two
+// folders are enough to wrap a plain sum.
+SRes sizes_checked(const Ar& a) {
+  uint64_t sum = 0;
+  for (const Folder& f : a.folders)
+    for (const uint64_t v : f.unpack_sizes) {
+      if (v >= (uint64_t(1) << 63) - sum) return SZ_ERROR_MEM;
+      sum += v;
+    }
+  return SZ_OK;
+}
+
 // SzArEx_Open2 (7zIn.c:1214-1312)
 SRes open_archive(const Byte* arc, size_t size, Archive& x) {
   if (size < kStartHeader) return SZ_ERROR_NO_ARCHIVE;
@@ -1039,6 +1058,7 @@ SRes open_archive(const Byte* arc, size_t size, Archive& x) {
     RINOK7(read_streams_info(s, &start, hx.db, ss, &have_ss));
     start += kStartHeader;
     if (hx.db.folders.size() != 1) return SZ_ERROR_ARCHIVE;
+    RINOK7(sizes_checked(hx.db));
     hx.folder_start_pack.assign(1, 0);
     hx.flags = x.flags;
     std::vector<Job> jobs(1, make_job(hx, hx.db, 0, start, arc, size));
@@ -1075,7 +1095,8 @@ SRes open_archive(const Byte* arc, size_t size, Archive& x) {
 
 SRes open_checked(const Byte* arc, size_t size, Archive& x, unsigned flags) {
   x.flags = flags;
-  const SRes r = open_archive(arc, size, x);
+  SRes r = open_archive(arc, size, x);
+  if (r == SZ_OK) r = sizes_checked(x.db);  // before any caller lays folders out
   if (r != SZ_OK) x = Archive();
   return r;
 }
@@ -1152,6 +1173,13 @@ static SRes sz_open(const Byte* archive, size_t size, LzmaGpu7zFolder* folders, 
   return SZ_OK;
 }
 
+// A file's range inside its folder's output.  A substream size is the folder's
+// size minus the sizes before it, which wraps where those exceed it (line
+// 7zIn.c:792 wraps the same way), so off + len is not formed.
+static bool file_fits(uint64_t off, uint64_t len, uint64_t unpack) {
+  return len <= unpack && off <= unpack - len;
+}
+
 static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t size,
                        SRes* file_res, size_t file_cap, unsigned flags) {
   const SizeT cap = *destLen;
@@ -1202,7 +1230,7 @@ static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t s
     for (size_t i = 0; i < nfiles; ++i) {
       const uint32_t fo = x.file_folder[i];
       if (fo == kNoFolder || jobs[fo].res != SZ_OK || !x.files[i].crc_defined) continue;
-      if (foff[i] + x.files[i].size > jobs[fo].unpack) continue;
+      if (!file_fits(foff[i], x.files[i].size, jobs[fo].unpack)) continue;
       off.push_back(jobs[fo].dst_off + foff[i]);
       len.push_back(x.files[i].size);
       tag.push_back(~int64_t(i));
@@ -1221,7 +1249,7 @@ static SRes sz_extract(Byte* dest, SizeT* destLen, const Byte* archive, size_t s
       if (fo == kNoFolder) continue;
       if (jobs[fo].res != SZ_OK) {
         fres[i] = jobs[fo].res;
-      } else if (foff[i] + x.files[i].size > jobs[fo].unpack) {
+      } else if (!file_fits(foff[i], x.files[i].size, jobs[fo].unpack)) {
         fres[i] = SZ_ERROR_FAIL;
       }
     }

@@ -216,6 +216,12 @@ SRes index_file(const Byte* f, size_t size, std::vector<LzmaGpuXzBlock>* blocks,
     for (LzmaGpuXzBlock& b : streams[k]) {
       b.stream = uint32_t(streams.size() - 1 - k);
       b.dst_off = dst;
+      // The reference guards this sum (ADD_SIZE_CHECH in Xzs_GetUnpackSize,
+      // XzIn.c:43-44, 254-261) and leaves its caller to look at the result.
+      // Here the sum becomes device ranges, so a total that wraps or reaches
+      // 2^63 ends the index, with the code XzIn.c:208-211 gives its own
+      // oversized sums.  Every caller of the index is behind this line.
+      if (b.unpack_size >= (uint64_t(1) << 63) - dst) return SZ_ERROR_ARCHIVE;
       dst += b.unpack_size;
       blocks->push_back(b);
     }

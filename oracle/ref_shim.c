@@ -179,3 +179,53 @@ int ref_7z_extract(const unsigned char *arc, size_t size, unsigned char *out, si
   *out_len = pos;
   return res;
 }
+
+/*
+ * xz backward index (Xzs_ReadBackward, XzIn.c:274-306) over an in-memory file
+ * through the seek stream above behind a CLookToRead.  Streams come out of the
+ * reference last first; here everything is returned in file order:
+ * stream_flags[s], and per block {stream, totalSize, unpackSize} as three
+ * UInt64s in blocks[].  *unpack_total = Xzs_GetUnpackSize, XZ_SIZE_OVERFLOW
+ * passed through.  Counts are complete even where the arrays are too small.
+ */
+int ref_xz_index(const unsigned char *file, size_t size, unsigned *n_streams,
+                 unsigned short *stream_flags, size_t stream_cap, unsigned long long *blocks,
+                 size_t block_cap, size_t *n_blocks, unsigned long long *unpack_total) {
+  ShimMemSeek ms;
+  CLookToRead look;
+  CXzs xzs;
+  Int64 start = 0;
+  SRes res;
+  size_t k, i, nb = 0;
+  xz_tables();
+  ms.s.Read = shim_seek_read;
+  ms.s.Seek = shim_seek_seek;
+  ms.data = file;
+  ms.size = size;
+  ms.pos = 0;
+  LookToRead_CreateVTable(&look, False);
+  look.realStream = &ms.s;
+  LookToRead_Init(&look);
+  Xzs_Construct(&xzs);
+  res = Xzs_ReadBackward(&xzs, &look.s, &start, 0, &g_shim_alloc);
+  *n_streams = 0;
+  *n_blocks = 0;
+  *unpack_total = 0;
+  if (res == SZ_OK) {
+    *n_streams = (unsigned)xzs.num;
+    *unpack_total = Xzs_GetUnpackSize(&xzs);
+    for (k = 0; k < xzs.num; k++) {
+      const CXzStream *st = &xzs.streams[xzs.num - 1 - k];
+      if (k < stream_cap) stream_flags[k] = st->flags;
+      for (i = 0; i < st->numBlocks; i++, nb++)
+        if (nb < block_cap) {
+          blocks[3 * nb] = k;
+          blocks[3 * nb + 1] = st->blocks[i].totalSize;
+          blocks[3 * nb + 2] = st->blocks[i].unpackSize;
+        }
+    }
+    *n_blocks = nb;
+  }
+  Xzs_Free(&xzs, &g_shim_alloc);
+  return res;
+}

@@ -9,6 +9,13 @@
 // fuzzer runs in the CPU container, where every decode entry returns
 // SZ_ERROR_FAIL before touching a device).  The first input byte picks the
 // parser.
+//
+// Memory errors are the sanitizers' to find; a wrong answer is not.  So after
+// every successful xz index and 7z open the tiling invariant is asserted: the
+// output ranges (xz blocks, 7z folders) follow each other from 0, none leaves
+// [0, total), no sum wraps and the total stays below 2^63 -- these ranges are
+// what the decode calls hand to the GPU.  An xz block's input ranges lie
+// inside the file.
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -16,6 +23,22 @@
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
+
+// a violated invariant ends the run like a sanitizer report does
+static void require(bool ok) {
+  if (!ok) __builtin_trap();
+}
+
+// one output range after the other from 0, inside [0, total), nothing wrapped
+struct Tiling {
+  uint64_t total, off = 0;
+  explicit Tiling(uint64_t t) : total(t) { require(t < (uint64_t(1) << 63)); }
+  void next(uint64_t dst_off, uint64_t size) {
+    require(dst_off == off && size <= total - off);
+    off += size;
+  }
+  void end() const { require(off == total); }
+};
 
 extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
   if (size < 1) return 0;
@@ -31,8 +54,12 @@ extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
         std::vector<LzmaGpu7zFolder> fo(nfo + 1);
         std::vector<LzmaGpu7zFile> fi(nfi + 1);
         std::vector<UInt16> names(nn + 1);
-        LzmaGpu_7zOpen(p, n, fo.data(), nfo, &nfo, fi.data(), nfi, &nfi, names.data(), nn, &nn,
-                       &total);
+        r = LzmaGpu_7zOpen(p, n, fo.data(), nfo, &nfo, fi.data(), nfi, &nfi, names.data(), nn, &nn,
+                           &total);
+        require(r == SZ_OK && nfo + 1 == fo.size());
+        Tiling t(total);
+        for (size_t i = 0; i < nfo; ++i) t.next(fo[i].dst_off, fo[i].unpack_size);
+        t.end();
       }
       break;
     }
@@ -41,7 +68,16 @@ extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
       uint64_t total = 0;
       if (LzmaGpu_XzIndex(p, n, nullptr, 0, &nb, &total) == SZ_OK && nb < (1u << 16)) {
         std::vector<LzmaGpuXzBlock> b(nb + 1);
-        LzmaGpu_XzIndex(p, n, b.data(), nb, &nb, &total);
+        require(LzmaGpu_XzIndex(p, n, b.data(), nb, &nb, &total) == SZ_OK && nb + 1 == b.size());
+        Tiling t(total);
+        for (size_t i = 0; i < nb; ++i) {
+          t.next(b[i].dst_off, b[i].unpack_size);
+          require(b[i].header_off < b[i].data_off && b[i].data_off <= n &&
+                  b[i].pack_size <= n - b[i].data_off &&
+                  b[i].check_off >= b[i].data_off + b[i].pack_size && b[i].check_off <= n &&
+                  b[i].check_size <= n - b[i].check_off);
+        }
+        t.end();
       }
       break;
     }

@@ -1,5 +1,6 @@
 """Seed corpora for the libFuzzer targets (TEST INFRASTRUCTURE): the committed
-golden fixtures, prefixed with the targets' selector bytes.
+golden fixtures and the hand-made xz files (tests/xz_handmade.py, generated),
+prefixed with the targets' selector bytes.
 
     python tests/fuzz/seeds.py OUTDIR   -> OUTDIR/containers/*, OUTDIR/lanes/*
 """
@@ -10,6 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(os.path.dirname(HERE), "golden")
+sys.path.insert(0, os.path.dirname(HERE))
 
 
 def _load(name, blob):
@@ -41,6 +43,9 @@ def write(out):
             if "off" in c and c["len"] < 400000:
                 put(con, b"\x01" + d["blob"][c["off"]:c["off"] + c["len"]])
                 put(con, b"\x02" + d["blob"][c["off"]:c["off"] + min(c["len"], 4096)])
+    import xz_handmade
+    for c in xz_handmade.all_cases():
+        put(con, b"\x01" + c["data"])
     g = _load("cases.json", "blob.bin")
     for c in g["cases"][:300]:
         if c["kind"] not in ("lzma", "lzma2"):

@@ -158,6 +158,40 @@ def test_open_huge_counts_do_not_allocate(L):
     assert r == 16, r
 
 
+def test_open_folder_sizes_that_wrap_are_refused(L):
+    """Folder outputs tile one device buffer.  7z numbers are full 64-bit, so
+    two folders whose sizes sum to a small number mod 2^64 would pass every
+    capacity check against the wrapped total and put the second folder far
+    outside the allocation.  The open refuses a sum that wraps or reaches 2^63
+    with SZ_ERROR_MEM -- what SzArEx_Extract returns when a folder's size cannot
+    be allocated (7zIn.c:1354-1369); the extract call opens through the same
+    check (open_checked).  Host calls only: such a file never goes to a GPU."""
+    import sevenzwrite as W
+    one = W.coder(W.M_COPY, b"")
+
+    def arc(a, b):
+        # kHeader kMainStreamsInfo | kPackInfo pos 0, 2 streams, kSize 5 5 kEnd |
+        # kUnpackInfo kFolder 2 external=0, two Copy folders, kCodersUnpackSize a b kEnd | kEnd kEnd
+        hdr = (bytes([0x01, 0x04, 0x06, 0x00, 0x02, 0x09, 0x05, 0x05, 0x00, 0x07, 0x0B, 0x02, 0x00])
+               + (b"\x01" + one) * 2 + bytes([0x0C]) + W.number(a) + W.number(b)
+               + bytes([0x00, 0x00, 0x00]))
+        return _with_header(hdr)
+
+    # the layout itself opens: two folders and, without kFilesInfo, no file
+    # (7zIn.c:981-982)
+    r, folders, files, _, total = L.sz_open(arc(5, 7))
+    assert (r, total, files) == (0, 12, [])
+    assert [(f.dst_off, f.unpack_size) for f in folders] == [(0, 5), (5, 7)]
+    for a, b in (((1 << 64) - 5, 10),                           # 5 mod 2^64
+                 ((1 << 63) + 1, (1 << 63) + 2),                # 3 mod 2^64
+                 ((1 << 63) - 1, 1), (1 << 63, 0), (0, 1 << 63)):   # reaches 2^63
+        r, folders, files, _, total = L.sz_open(arc(a, b))
+        assert (r, folders, files, total) == (2, [], [], 0), (a, b, r, total)
+    r, folders, _, _, total = L.sz_open(arc((1 << 63) - 2, 1))  # the largest sum that opens
+    assert (r, total) == (0, (1 << 63) - 1)
+    assert [(f.dst_off, f.unpack_size) for f in folders] == [(0, (1 << 63) - 2), ((1 << 63) - 2, 1)]
+
+
 @pytest.mark.gpu
 def test_gpu_7z_fixtures(L):
     d = fixtures()
