@@ -16,7 +16,6 @@
 #include <exception>
 #include <mutex>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
@@ -92,70 +91,10 @@ extern "C" {
 
 // ------------------------------------------------------------------ batch extension
 
-// Workspace: each item gets a 16-byte aligned slice of table_cells() cells
-// (LZMA2 ranges: the lc+lp=4, pb=4 maximum).  Returns per-item lo-table
-// widths (0 = not LDS-eligible) through lo_w when given.
-// `skip` (optional): items whose global sections live in a class slot area
-// (lane-interleaved throughput classes) get no slice (probs_off 0, unused).
-static uint64_t plan_workspace(LzmaGpuStreamDesc* descs, size_t n, std::vector<uint32_t>* lo_w,
-                               std::vector<uint32_t>* lat_w = nullptr,
-                               const std::vector<uint8_t>* skip = nullptr) {
-  uint64_t off = 0;
-  if (lo_w) lo_w->assign(n, 0);
-  if (lat_w) lat_w->assign(n, 0);
-  for (size_t i = 0; i < n; ++i) {
-    LzmaGpuStreamDesc& d = descs[i];
-    if (skip && (*skip)[i]) {
-      d.probs_off = 0;
-      continue;
-    }
-    uint32_t np = 0;
-    if (d.kind == LZMA_GPU_KIND_LZMA2) {
-      np = lzgpu::table_cells(4, 0, 4);
-      if (lo_w && d.props[0] <= 40) (*lo_w)[i] = lzgpu::lzma2_lds_cells(LZGPU_LDS_MASK);
-      if (lat_w && d.props[0] <= 40) (*lat_w)[i] = lzgpu::lzma2_lds_cells(LZGPU_LDS_MASK_LAT);
-    } else {
-      uint32_t lc, lp, pb, dict;
-      if (lzgpu::lz_props_parse(d.props, d.props_size, lc, lp, pb, dict) == SZ_OK) {
-        np = lzgpu::table_cells(lc, lp, pb);
-        if (lo_w) (*lo_w)[i] = lzgpu::make_layout(lc, lp, pb, LZGPU_LDS_MASK).lds_cells;
-        if (lat_w) (*lat_w)[i] = lzgpu::make_layout(lc, lp, pb, LZGPU_LDS_MASK_LAT).lds_cells;
-      }
-    }
-    d.probs_off = off;
-    off += (uint64_t(np) + 7) & ~uint64_t(7);
-  }
-  return off * 2;
-}
-
-// LDS cells of an item's slice under the slot-global latency placement
-// (lzgpu::kLdsMaskLatSlotG); 0 = bad props
-static uint32_t lat_slotg_cells(const LzmaGpuStreamDesc& d) {
-  if (d.kind == LZMA_GPU_KIND_LZMA2)
-    return d.props[0] <= 40 ? lzgpu::lzma2_lds_cells(lzgpu::kLdsMaskLatSlotG) : 0u;
-  uint32_t lc, lp, pb, dict;
-  if (lzgpu::lz_props_parse(d.props, d.props_size, lc, lp, pb, dict) != SZ_OK) return 0;
-  return lzgpu::make_layout(lc, lp, pb, lzgpu::kLdsMaskLatSlotG).lds_cells;
-}
-
-static size_t plan_simple(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order) {
-  std::vector<uint32_t> w;
-  const uint64_t bytes = plan_workspace(descs, n, &w);
-  if (order) {
-    std::vector<uint32_t> idx(n);
-    std::iota(idx.begin(), idx.end(), 0u);
-    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) {
-      if (descs[a].dst_cap != descs[b].dst_cap) return descs[a].dst_cap > descs[b].dst_cap;
-      return w[a] > w[b];
-    });
-    for (size_t i = 0; i < n; ++i) order[i] = idx[i];
-  }
-  return size_t(bytes);
-}
-
+// The planner is decode_plan.h (plan_simple, plan_batch); its entry points:
 size_t LzmaGpu_PlanBatch(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order) {
   try {
-    return plan_simple(descs, n, order);
+    return lzgpu_host::plan_simple(descs, n, order);
   } catch (const std::exception&) {
     set_error("plan: host allocation failed");
     return 0;
@@ -204,341 +143,18 @@ static LzmaGpuPlanOptions env_options() {
   return o;
 }
 
-// Launch shape of one LDS class: `stride` cells per stream, `count` streams,
-// `cus` CUs.  `regime`: 0 = by the batch (throughput when LDS holds >= 64
-// streams per CU and the batch fills them), 1 = throughput shape forced,
-// 2 = latency shape (one stream per wave) forced.
-static LzmaGpuLdsClass plan_lds_class(uint32_t stride, uint64_t count, uint32_t mask,
-                                      uint32_t cus, int regime, const LzmaGpuPlanOptions& o,
-                                      bool* latency = nullptr, bool any_groups = false,
-                                      bool allow_fit = false) {
-  LzmaGpuLdsClass c;
-  memset(&c, 0, sizeof c);
-  c.lds_mask = mask;
-  // Per-lane slice: an odd number of dwords, so that the 32 lanes of a wave
-  // reading the same cell index (literal-tree top levels, IsRep of one state)
-  // fall in 32 different LDS banks (bank = dword mod 32 for 2- and 4-byte
-  // reads); 8-byte aligned slices (158 dwords at lc0/pb0) put lanes l and
-  // l + 16 in one bank.  Cells are read 2 or 4 bytes at a time: 4-byte
-  // aligned slices suffice.
-  if (o.flags & LZMA_GPU_PLAN_SLICE_ALIGN8)
-    stride = (stride + 3) & ~3u;
-  else
-    stride = ((stride + 1) & ~1u) | 2u;  // cells = 2 mod 4: odd dword count
-  const uint32_t lds_per_cu = 160 * 1024;
-  const uint32_t per_cu = std::max<uint32_t>(1, lds_per_cu / (stride * 2));  // streams/CU
-  uint32_t occ = 4;
-  const uint32_t occ_over = o.waves_per_simd;
-  if (occ_over == 1 || occ_over == 2 || occ_over == 4 || occ_over == 6 || occ_over == 8)
-    occ = occ_over;
-  // Two regimes (profiles/r01_variants v17-v28):
-  //  * throughput -- LDS holds >= 64 streams per CU and the batch fills them:
-  //    up to 32 streams per wave with at least 8 waves per CU (64K x 4 KiB:
-  //    32 lanes x 8 waves per CU).  A VALU instruction of a wave whose active
-  //    lanes all sit in its low half costs one pass whether 16 or 32 lanes are
-  //    active, so 32 lanes halve the instructions per stream (ubench:
-  //    scripts/ubench/lit_ubench.hip; v38-v41: 24.6 -> 27.0 GB/s with the
-  //    checkpoint reader);
-  //  * latency -- few streams per CU (small batches, or wide lc+lp tables):
-  //    one stream per wave, 16 waves per CU (config 2: 5.8 GB/s vs 2.5 GB/s
-  //    with 4 lanes x 4 waves; config 5: 2.6 GB/s vs 2.2 GB/s with 2 lanes).
-  // Throughput shapes keep lanes and workgroups per CU powers of two; every
-  // count is checked in LDS blocks below (lds_groups_fit).
-  auto pow2floor = [](uint32_t v) {
-    while (v & (v - 1)) v &= v - 1;
-    return v;
-  };
-  const uint64_t per_cu_batch = (count + cus - 1) / cus;
-  const bool thr = regime == 1 || (regime == 0 && per_cu >= 64 && per_cu_batch >= 64);
-  uint32_t lanes = 1, groups = 16;
-  if (latency) *latency = !thr;
-  if (thr) {
-    lanes = std::max<uint32_t>(1, std::min<uint32_t>(32, pow2floor(std::max<uint32_t>(1, per_cu / 8))));
-    groups = pow2floor(std::max<uint32_t>(1, std::min<uint32_t>(per_cu / lanes, 16)));
-  } else {
-    // one lane per wave: as many waves as LDS allows -- counted in the CU's
-    // 1,280-byte LDS blocks (lzgpu_host::lds_groups_fit) -- up to the 16 the
-    // register budget keeps resident.  Round 1's "a power of two, 6 / 10 / 12
-    // per CU run 10-30 % slower" was this count taken in bytes: the padded
-    // slices of 6, 10, 12 or 15 workgroups do not all fit, the last one waits
-    // for the queue to drain (config 5: 15 planned, 14 resident, 5.6 GB/s;
-    // 14 planned 7.2, profiles/r05_cfg5groups/)
-    groups = std::min<uint32_t>(lzgpu_host::lds_groups_fit(size_t(stride) * 2), 16);
-    (void)any_groups;
-    // Fitted latency shape (strong-scaling shares, profiles/r03_shares/): a
-    // batch of 17-63 streams per CU would run one-stream waves in two or more
-    // rounds; widen the waves instead so that every stream is resident at
-    // once -- 8,192 x 4 KiB (32 per CU): 2 lanes x 16 waves 5.64 ms vs 7.46 ms
-    // in two rounds (and vs 5.95 ms for 4-lane throughput waves).  Only for a
-    // batch that is one class (mixed-width batches merge their one-lane
-    // classes instead: config 5 4.58 GB/s fitted vs 5.00).
-    // LZMA_GPU_PLAN_NO_THR_FIT: the round-2 shape.
-    if (allow_fit && !(o.flags & LZMA_GPU_PLAN_NO_THR_FIT) && regime != 2 &&
-        per_cu_batch > groups && per_cu_batch < 64 && groups > 0) {
-      uint32_t want = uint32_t((per_cu_batch + groups - 1) / groups);
-      uint32_t l = 1;
-      while (l < want) l <<= 1;
-      while (l > 1 && uint64_t(l) * groups > per_cu) l >>= 1;
-      lanes = l;
-    }
-  }
-  const uint32_t over = o.lanes_per_group;
-  if (over > 0 && over <= 64 && over * stride * 2 <= lds_per_cu) {
-    lanes = over;
-    groups = pow2floor(std::max<uint32_t>(1, std::min<uint32_t>(per_cu / lanes, 16)));
-  }
-  if (occ_over) groups = std::min<uint32_t>(groups, 4 * occ);
-  // every planned workgroup resident at once, in whole LDS blocks
-  const uint32_t fit = lzgpu_host::lds_groups_fit(size_t(lanes) * stride * 2);
-  while (groups > 1 && groups > fit) groups = lanes == 1 ? groups - 1 : pow2floor(groups - 1);
-  const uint32_t g_over = o.groups_per_cu;
-  if (g_over > 0 && g_over <= fit) groups = g_over;
-  c.n = count;
-  c.lanes_per_group = lanes;
-  c.lds_cells_per_lane = stride;
-  c.groups_per_cu = std::max<uint32_t>(1, groups);
-  // register budget = the waves per SIMD that are actually resident (one
-  // wave per workgroup): 8 workgroups per CU -> 2 waves/SIMD -> 256 VGPRs,
-  // enough for the decoder state without spills
-  c.waves_per_simd = occ_over ? occ : std::max<uint32_t>(1, (c.groups_per_cu + 3) / 4);
-  return c;
-}
-
-// LDS class of a stream by its table width (cells): narrow tables share a
-// launch with many streams per CU, wide ones (lc + lp >= 3) get their own.
-static int lds_bucket(uint32_t cells) {
-  if (cells <= 768) return 0;
-  if (cells <= 1536) return 1;
-  if (cells <= 3072) return 2;
-  return 3;
-}
-
-// cells of an item's whole table (every section in LDS); 0 = bad props
-static uint32_t all_cells(const LzmaGpuStreamDesc& d) {
-  if (d.kind == LZMA_GPU_KIND_LZMA2) return d.props[0] <= 40 ? lzgpu::table_cells(4, 0, 4) : 0u;
-  uint32_t lc, lp, pb, dict;
-  if (lzgpu::lz_props_parse(d.props, d.props_size, lc, lp, pb, dict) != SZ_OK) return 0;
-  return lzgpu::table_cells(lc, lp, pb);
-}
-
-static SRes plan_batch(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order, LzmaGpuPlan* plan,
-                       const LzmaGpuPlanOptions& o) {
-  if (!order || !plan) return SZ_ERROR_PARAM;
-  if (o.kernel > LZMA_GPU_KERNEL_GLOBAL) return SZ_ERROR_PARAM;
-  memset(plan, 0, sizeof *plan);
-  std::vector<uint32_t> w, w_lat;
-  plan->workspace_bytes = plan_workspace(descs, n, &w, &w_lat);
-  plan->n = n;
-  const uint32_t cus = o.cus ? o.cus : device_cus();
-  // LDS-eligible: lo table <= 16384 cells (32 KiB, >= 5 streams per CU)
-  const uint32_t kMaxLdsCells = 16384;
-  const bool global_only = o.kernel == LZMA_GPU_KERNEL_GLOBAL;
-  const bool one_class = o.one_class != 0;
-  std::vector<uint32_t> bucket_idx[LZMA_GPU_MAX_CLASSES], glob_idx;
-  uint32_t bucket_stride[LZMA_GPU_MAX_CLASSES] = {0, 0, 0, 0};
-  for (size_t i = 0; i < n; ++i) {
-    if (!global_only && w[i] != 0 && w[i] <= kMaxLdsCells) {
-      const int b = one_class ? 0 : lds_bucket(w[i]);
-      bucket_idx[b].push_back(uint32_t(i));
-      bucket_stride[b] = std::max(bucket_stride[b], w[i]);
-    } else {
-      glob_idx.push_back(uint32_t(i));
-    }
-  }
-  // Longest work first, and streams of similar work side by side: a wave
-  // runs until its slowest lane is done.  Work ~ range-coder decisions, which
-  // track the compressed bits (~1.5 decisions per input bit on text), plus a
-  // little per output byte for literals writes and match copies.
-  auto work = [&](uint32_t i) { return 24 * descs[i].src_len + descs[i].dst_cap; };
-  auto by_len = [&](uint32_t a, uint32_t b) {
-    const uint64_t wa = work(a), wb = work(b);
-    if (wa != wb) return wa > wb;
-    return w[a] > w[b];
-  };
-  // One class per width bucket: the throughput placement first; a class that
-  // lands in the latency regime is re-planned with the latency placement (more
-  // tables in LDS, few streams per CU); few streams per CU go cooperative.
-  // The cooperative kernel is for few streams per CU -- counted over every
-  // LDS-eligible stream of the batch, since the classes run side by side and
-  // share the CUs (round 6: config 5's 4,096-stream share -- 16 per CU -- was
-  // four classes of ~4 per CU, each planned cooperative with the whole CU's
-  // LDS to itself and then starved of it when launched together: 246 ms,
-  // against 132 ms for 16,384 streams of the same mix)
-  size_t lds_total = 0;
-  for (int b = 0; b < LZMA_GPU_MAX_CLASSES; ++b) lds_total += bucket_idx[b].size();
-  const uint64_t per_cu_lds = (lds_total + cus - 1) / cus;
-  auto plan_bucket = [&](const std::vector<uint32_t>& idx, uint32_t stride_lo,
-                         bool any_groups, bool allow_fit = false) -> LzmaGpuLdsClass {
-    bool lat = false;
-    const int regime = o.kernel == LZMA_GPU_KERNEL_THROUGHPUT ? 1 : 0;
-    LzmaGpuLdsClass c = plan_lds_class(stride_lo, idx.size(), LZGPU_LDS_MASK, cus, regime, o, &lat);
-    const bool want_lat = o.kernel == LZMA_GPU_KERNEL_LATENCY || o.kernel == LZMA_GPU_KERNEL_COOP ||
-                          (o.kernel == LZMA_GPU_KERNEL_AUTO && lat);
-    if (!want_lat) return c;
-    uint32_t stride_lat = 0;
-    for (uint32_t i : idx) stride_lat = std::max(stride_lat, w_lat[i]);
-    if (stride_lat > kMaxLdsCells) return c;
-    c = plan_lds_class(stride_lat, idx.size(), LZGPU_LDS_MASK_LAT, cus,
-                       o.kernel == LZMA_GPU_KERNEL_AUTO ? 0 : 2, o, nullptr, any_groups,
-                       allow_fit);
-    // few streams per CU: the wave-cooperative kernel (all 32 lanes on one
-    // stream, copies and direct bits spread over the lanes) -- config 4
-    // 1.71 -> 2.85 GB/s and the xz leg 1.45 -> 2.36 at 4 streams per CU;
-    // at 16 per CU (config 2) the single-lane waves are faster (5.9 vs 5.2)
-    const uint64_t per_cu_batch = (idx.size() + cus - 1) / cus;
-    const bool coop = o.kernel == LZMA_GPU_KERNEL_COOP ||
-                      (o.kernel == LZMA_GPU_KERNEL_AUTO &&
-                       (o.coop == 1 || (o.coop == 0 && per_cu_lds <= 8)));
-    if (c.lanes_per_group == 1 && coop) {
-      c.lds_mask = LZGPU_LDS_MASK_LAT | lzgpu::kCoopBit;
-      if (!(o.flags & LZMA_GPU_PLAN_COOP_LAT)) {
-        // the whole table in LDS if it still fits the streams per CU the
-        // latency plan gives this class: no global round trip left in the
-        // match path (SpecPos, LenHigh) or the matched literal
-        uint32_t stride_all = 0;
-        for (uint32_t i : idx) stride_all = std::max(stride_all, all_cells(descs[i]));
-        if (stride_all != 0 && stride_all <= kMaxLdsCells) {
-          LzmaGpuLdsClass ca = plan_lds_class(stride_all, idx.size(),
-                                              LZGPU_LDS_MASK_ALL | lzgpu::kCoopBit, cus, 2, o);
-          const uint64_t want = std::min<uint64_t>(per_cu_batch, c.groups_per_cu);
-          if (ca.lanes_per_group == 1 && ca.groups_per_cu >= want) c = ca;
-        }
-      }
-    }
-    // more streams per CU than the widest slice lets resident: the slot trees
-    // to the global rows where that fits more one-stream workgroups per CU
-    // (config 5: 14 -> 16)
-    if (c.lds_mask == LZGPU_LDS_MASK_LAT && c.lanes_per_group == 1 && c.groups_per_cu < 16 &&
-        per_cu_batch > c.groups_per_cu && !(o.flags & LZMA_GPU_PLAN_NO_SLOTG)) {
-      uint32_t stride_sg = 0;
-      for (uint32_t i : idx) stride_sg = std::max(stride_sg, lat_slotg_cells(descs[i]));
-      if (stride_sg != 0 && stride_sg <= kMaxLdsCells) {
-        const LzmaGpuLdsClass cs =
-            plan_lds_class(stride_sg, idx.size(), lzgpu::kLdsMaskLatSlotG, cus,
-                           o.kernel == LZMA_GPU_KERNEL_AUTO ? 0 : 2, o, nullptr, any_groups);
-        if (cs.lanes_per_group == 1 && cs.groups_per_cu > c.groups_per_cu) c = cs;
-      }
-    }
-    return c;
-  };
-  // Several buckets in the one-lane latency regime (mixed-props batches,
-  // config 5) become one class: its lanes draw from one queue in one launch,
-  // so the batch has one tail instead of one per class, and its workgroup
-  // count per CU is what the widest slice allows (up to 16, any number: the
-  // queue balances the SIMDs) -- config 5 4.6-4.8 -> 4.9 GB/s, and steadier
-  // (profiles/r02_ab/cfg5_merge_lat_ab.log).  LZMA_GPU_PLAN_NO_MERGE_LAT keeps
-  // one class per bucket.
-  int merged = -1;  // the bucket holding the merged latency class
-  if (!one_class && !(o.flags & LZMA_GPU_PLAN_NO_MERGE_LAT)) {
-    int lat_b[LZMA_GPU_MAX_CLASSES], n_lat = 0;
-    for (int b = 0; b < LZMA_GPU_MAX_CLASSES; ++b) {
-      if (bucket_idx[b].empty()) continue;
-      const LzmaGpuLdsClass c = plan_bucket(bucket_idx[b], bucket_stride[b], false);
-      if ((c.lds_mask == LZGPU_LDS_MASK_LAT || c.lds_mask == lzgpu::kLdsMaskLatSlotG) &&
-          c.lanes_per_group == 1)
-        lat_b[n_lat++] = b;
-    }
-    if (n_lat >= 2) {
-      const int t = lat_b[0];
-      for (int j = 1; j < n_lat; ++j) {
-        const int b = lat_b[j];
-        bucket_idx[t].insert(bucket_idx[t].end(), bucket_idx[b].begin(), bucket_idx[b].end());
-        bucket_stride[t] = std::max(bucket_stride[t], bucket_stride[b]);
-        bucket_idx[b].clear();
-      }
-      merged = t;
-    }
-  }
-  int n_buckets = 0;
-  for (int b = 0; b < LZMA_GPU_MAX_CLASSES; ++b) n_buckets += bucket_idx[b].empty() ? 0 : 1;
-  size_t k = 0;
-  uint64_t best = 0;
-  std::vector<uint8_t> in_slots;  // items of lane-interleaved classes
-  uint64_t slot_total[LZMA_GPU_MAX_CLASSES] = {0, 0, 0, 0};
-  for (int b = 0; b < LZMA_GPU_MAX_CLASSES; ++b) {
-    if (bucket_idx[b].empty()) continue;
-    std::stable_sort(bucket_idx[b].begin(), bucket_idx[b].end(), by_len);
-    for (uint32_t i : bucket_idx[b]) order[k++] = i;
-    LzmaGpuLdsClass c = plan_bucket(bucket_idx[b], bucket_stride[b], b == merged,
-                                    n_buckets == 1);
-    if (o.flags & LZMA_GPU_PLAN_KERNEL_LZMA2) c.flags |= LZMA_GPU_CLASS_HAS_LZMA2;
-    for (uint32_t i : bucket_idx[b])
-      if (descs[i].kind == LZMA_GPU_KIND_LZMA2) {
-        c.flags |= LZMA_GPU_CLASS_HAS_LZMA2;
-        break;
-      }
-    const bool ilv_any = (o.flags & LZMA_GPU_PLAN_ILV_ANY) != 0;
-    if (!(o.flags & LZMA_GPU_PLAN_NO_ILV) && c.lds_mask == LZGPU_LDS_MASK &&
-        (c.lanes_per_group == 32 || c.lanes_per_group == 64 || (ilv_any && c.lanes_per_group <= 64))) {
-      // lane-interleaved global sections: one column per resident lane (the
-      // lanes keep it across the streams they take from the queue); config 3
-      // 28.1 -> 29.9 GB/s (profiles/r02_ilv/ilv_ab.log).  Only for whole lane
-      // groups: a narrower workgroup would leave most of every row unused.
-      uint32_t rows = 0;
-      for (uint32_t i : bucket_idx[b]) {
-        const LzmaGpuStreamDesc& d = descs[i];
-        uint32_t lc = 4, lp = 0, pb = 4, dict;
-        if (d.kind != LZMA_GPU_KIND_LZMA2 &&
-            lzgpu::lz_props_parse(d.props, d.props_size, lc, lp, pb, dict) != SZ_OK)
-          continue;
-        rows = std::max(rows, lzgpu::make_layout(lc, lp, pb, LZGPU_LDS_MASK).glb_cells);
-      }
-      const uint64_t grid = (c.n + c.lanes_per_group - 1) / c.lanes_per_group;
-      const uint64_t groups =
-          o.persistent == 2 ? grid : std::min<uint64_t>(grid, uint64_t(cus) * c.groups_per_cu);
-      const uint64_t lane_groups = (c.lanes_per_group + lzgpu::kIlv - 1) / lzgpu::kIlv;
-      c.slot_cells = std::max<uint32_t>((rows + 1) & ~1u, 2);  // even: pairs of cells
-      c.slot_groups = uint32_t(groups);
-      slot_total[plan->n_classes] = groups * lane_groups * lzgpu::kIlv * c.slot_cells;
-      c.lds_mask |= lzgpu::kIlvBit;
-      if (in_slots.empty()) in_slots.assign(n, 0);
-      for (uint32_t i : bucket_idx[b]) in_slots[i] = 1;
-    }
-    plan->classes[plan->n_classes++] = c;
-    plan->n_lds += c.n;
-    if (c.n > best) {
-      best = c.n;
-      plan->lanes_per_group = c.lanes_per_group;
-      plan->lds_cells_per_lane = c.lds_cells_per_lane;
-      plan->groups_per_cu = c.groups_per_cu;
-      plan->waves_per_simd = c.waves_per_simd;
-    }
-  }
-  std::stable_sort(glob_idx.begin(), glob_idx.end(), by_len);
-  for (uint32_t i : glob_idx) order[k++] = i;
-  plan->persistent = o.persistent == 2 ? 0u : 1u;
-  // per-stream slices only for items outside the slot areas, then the slot
-  // areas (128-byte aligned), then the LDS launches' work counters
-  uint64_t ws_cells = plan->workspace_bytes / 2;
-  if (!in_slots.empty()) ws_cells = plan_workspace(descs, n, nullptr, nullptr, &in_slots) / 2;
-  for (uint32_t c = 0; c < plan->n_classes; ++c) {
-    if (!slot_total[c]) continue;
-    ws_cells = (ws_cells + 63) & ~uint64_t(63);
-    plan->classes[c].slot_off = ws_cells;
-    ws_cells += slot_total[c];
-  }
-  plan->workspace_bytes = ws_cells * 2;
-  plan->queue_offset = (plan->workspace_bytes + 63) & ~uint64_t(63);
-  plan->workspace_bytes = plan->queue_offset + 64 * LZMA_GPU_MAX_CLASSES;
-  return SZ_OK;
+SRes LzmaGpu_PlanBatchEx(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order, LzmaGpuPlan* plan) {
+  return LzmaGpu_PlanBatchOpt(descs, n, order, plan, nullptr);
 }
 
 // C ABI: no exception crosses it (host allocation failure -> SZ_ERROR_MEM).
-static SRes plan_batch_nothrow(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order,
-                               LzmaGpuPlan* plan, const LzmaGpuPlanOptions& o) {
-  return lzgpu_host::guarded("plan: host allocation failed",
-                             [&]() { return plan_batch(descs, n, order, plan, o); });
-}
-
-SRes LzmaGpu_PlanBatchEx(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order,
-                         LzmaGpuPlan* plan) {
-  return plan_batch_nothrow(descs, n, order, plan, env_options());
-}
-
 SRes LzmaGpu_PlanBatchOpt(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order, LzmaGpuPlan* plan,
                           const LzmaGpuPlanOptions* opt) {
   if (opt && (opt->flags & ~LZMA_GPU_PLAN_KNOWN_FLAGS)) return SZ_ERROR_PARAM;
-  return plan_batch_nothrow(descs, n, order, plan, opt ? *opt : env_options());
+  const LzmaGpuPlanOptions o = opt ? *opt : env_options();
+  return lzgpu_host::guarded("plan: host allocation failed", [&]() {
+    return lzgpu_host::plan_batch(descs, n, order, plan, o, o.cus ? o.cus : device_cus());
+  });
 }
 
 // Internal streams for concurrent class launches: a pool per device, guarded
@@ -655,11 +271,8 @@ SRes LzmaGpu_DecodeBatchEx(const LzmaGpuPlan* plan, const LzmaGpuStreamDesc* d_d
         break;
       }
     }
-    if (lzgpu_launch_decode_lds(d_descs, d_order + first, uint32_t(c.n), d_src, d_dst, ws,
-                                d_results, c.lanes_per_group, c.lds_cells_per_lane,
-                                c.waves_per_simd, c.groups_per_cu, max_groups, queue, c.lds_mask,
-                                c.flags, LzgpuSlots{c.slot_off, c.slot_cells, c.slot_groups},
-                                sk) != 0) {
+    const LzgpuDecodeBufs bufs{d_descs, d_order + first, d_src, d_dst, ws, d_results, queue};
+    if (lzgpu_launch_decode_lds(c, bufs, max_groups, sk) != 0) {
       set_error("LDS decode kernel launch failed");
       ret = SZ_ERROR_FAIL;
       break;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "decode_plan.h"
 #include "lzma_lane.h"
 
 // Devices the library keeps per-device state for (launch attributes, class
@@ -25,22 +26,30 @@ int lzgpu_allow_full_lds(const void* kfn);
 // largest table (cells) the cooperative session kernel stages in LDS: lc+lp <= 4
 // at any pb (LZMA2's bound, 28 KiB) and wider LZMA tables up to 64 KiB
 constexpr uint32_t kSessCoopMaxCells = 32768;
-// Slot area of a lane-interleaved class (LZMA_GPU_PLAN_ILV): `off` cells into
-// the workspace, `cells` rows of kIlv cells per lane group, room for `groups`
-// workgroups.
-struct LzgpuSlots {
-  uint64_t off;
-  uint32_t cells;
-  uint32_t groups;
+// One LDS class of a plan (c.n streams; order and queue the class's own) with the
+// kernel and launch shape decode_plan.h gives it, at most max_groups workgroups
+// (0 = no cap).  -1: no kernel is built for the class, or the launch failed.
+struct LzgpuDecodeBufs {
+  const LzmaGpuStreamDesc* descs;
+  const uint32_t* order;
+  const uint8_t* src;
+  uint8_t* dst;
+  uint16_t* ws;
+  LzmaGpuResult* results;
+  uint32_t* queue;
 };
-extern "C" int lzgpu_launch_decode_lds(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order,
-                                       uint32_t n, const uint8_t* d_src, uint8_t* d_dst,
-                                       uint16_t* d_ws, LzmaGpuResult* d_results, uint32_t lanes,
-                                       uint32_t stride, uint32_t waves_per_simd,
-                                       uint32_t groups_per_cu, uint32_t max_groups,
-                                       uint32_t* d_queue, uint32_t lds_mask,
-                                       uint32_t class_flags, LzgpuSlots slots,
-                                       hipStream_t stream);
+extern "C" int lzgpu_launch_decode_lds(const LzmaGpuLdsClass& c, const LzgpuDecodeBufs& b,
+                                       uint32_t max_groups, hipStream_t stream);
+// The launchers' own shapes, for tests (cus 0 = the current device's, env null =
+// the process's LZGPU_DUP / LZGPU_WIN): 1 = *out filled, 0 = no kernel.
+extern "C" int lzgpu_decode_launch_shape(const LzmaGpuLdsClass* c, uint32_t n, uint32_t max_groups,
+                                         uint32_t cus, const lzgpu_host::LaunchEnv* env,
+                                         lzgpu_host::LaunchShape* out);
+extern "C" int lzgpu_session_launch_shape(uint32_t n, uint32_t lds_cells, uint32_t max_groups,
+                                          uint32_t cus, const lzgpu_host::LaunchEnv* env,
+                                          lzgpu_host::LaunchShape* out);
+// rows[4 i ..] = (family, w, mask, k2) of kernel table row i < cap; returns the row count
+extern "C" uint32_t lzgpu_decode_kernel_rows(uint32_t* rows, uint32_t cap);
 extern "C" int lzgpu_launch_crc_arrays(const uint8_t* d_data, const uint64_t* d_off,
                                        const uint64_t* d_len, uint32_t n,
                                        const uint32_t* d_chunk_base,
@@ -92,26 +101,6 @@ extern "C" int lzgpu_launch_sha256(const uint8_t* d_data, const uint64_t* d_off,
 // host-side helpers shared by the C-ABI translation units (lzma_capi.hip)
 namespace lzgpu_host {
 
-// LDS is given to a workgroup in whole blocks: 128 blocks of 1,280 bytes make a
-// CU's 160 KiB (measured, profiles/r05_cfg5groups/: a launch padded to 160 KiB
-// / 15 = 10,752 bytes per workgroup fitted 14 per CU, not 15 -- 9 blocks
-// each).  Workgroup counts and the LDS padding that forces them are computed in
-// blocks.
-constexpr uint32_t kLdsBytesPerCu = 160u * 1024u;
-constexpr uint32_t kLdsGrain = 1280u;
-constexpr uint32_t kLdsBlocksPerCu = kLdsBytesPerCu / kLdsGrain;
-inline uint32_t lds_blocks(size_t bytes) {
-  return uint32_t((bytes + kLdsGrain - 1) / kLdsGrain);
-}
-// workgroups of `bytes` of LDS that fit a CU at once
-inline uint32_t lds_groups_fit(size_t bytes) {
-  const uint32_t b = lds_blocks(bytes);
-  return b ? kLdsBlocksPerCu / b : 0xFFFFu;
-}
-// the most LDS each of `groups` workgroups can take with all of them resident
-inline size_t lds_share(uint32_t groups) {
-  return size_t(kLdsBlocksPerCu / (groups ? groups : 1u)) * kLdsGrain;
-}
 bool ensure_device();
 void set_error(const char* what);
 bool hip_ok(hipError_t e, const char* what);

@@ -3,8 +3,8 @@
 // lzgpu_decode_lds_kernel (fast path, LZMA items whose lo table fits LDS):
 //   one stream per lane, L lanes per workgroup (one wave with L active
 //   lanes), each lane's lo probability table in its own LDS slice of
-//   `stride` cells; the planner picks L so that about four workgroups share a
-//   CU's 160 KiB.  The hardware dispatcher starts a new workgroup whenever
+//   `stride` cells (L and the workgroups per CU: decode_plan.h).  The
+//   hardware dispatcher starts a new workgroup whenever
 //   one retires, so a 64K-stream batch streams through the chip in waves of
 //   resident workgroups with no host round trips.
 // lzgpu_decode_batch_kernel (generic: any lc/lp/pb, LZMA2 ranges): 64 lanes
@@ -234,45 +234,34 @@ __global__ void __launch_bounds__(32) lzgpu_session_coop_kernel(LzgpuSession* __
   }
 }
 
-// Window for a launch of `grid` one-wave workgroups whose tables take
-// `table_bytes` of LDS: the largest power of two that still leaves room for
-// every workgroup a CU holds at once (one each while the grid fits the CUs),
-// at most 128 KiB; 0 (no window) below 4 KiB.  LZGPU_WIN=0 disables it.
-static uint32_t window_bytes(uint64_t grid, size_t table_bytes, uint32_t groups_per_cu) {
-  static const bool off = [] {
-    const char* e = getenv("LZGPU_WIN");
-    return e && e[0] == '0';
+// LZGPU_DUP=D (A/B; D = 1 launches the one-lane kernel) and LZGPU_WIN=0 (no LDS
+// history window), read once per process
+static const lzgpu_host::LaunchEnv& launch_env() {
+  static const lzgpu_host::LaunchEnv env = [] {
+    const char *d = getenv("LZGPU_DUP"), *w = getenv("LZGPU_WIN");
+    return lzgpu_host::LaunchEnv{d ? atoi(d) : kLaneDup, (w && w[0] == '0') ? 1u : 0u};
   }();
-  if (off) return 0;
-  const uint32_t cus = lzgpu_host::device_cus();
-  uint64_t per_cu = (grid + cus - 1) / cus;
-  if (groups_per_cu && per_cu > groups_per_cu) per_cu = groups_per_cu;
-  if (per_cu == 0) per_cu = 1;
-  const size_t share = lzgpu_host::lds_share(per_cu);
-  const size_t tb = (table_bytes + 15) & ~size_t(15);
-  if (share <= tb + 4096) return 0;
-  uint32_t w = 1u << 17;
-  while (w > share - tb) w >>= 1;
-  return w >= 4096 ? w : 0;
+  return env;
+}
+
+extern "C" int lzgpu_session_launch_shape(uint32_t n, uint32_t lds_cells, uint32_t max_groups,
+                                          uint32_t cus, const lzgpu_host::LaunchEnv* env,
+                                          lzgpu_host::LaunchShape* out) {
+  return lzgpu_host::session_launch_shape(n, lds_cells, max_groups,
+                                          cus ? cus : lzgpu_host::device_cus(),
+                                          env ? *env : launch_env(), *out);
 }
 
 extern "C" int lzgpu_launch_session_coop(LzgpuSession* d_sess, uint32_t n, uint32_t lds_cells,
                                          uint32_t max_groups, hipStream_t stream) {
   if (n == 0) return 0;
-  if (lds_cells == 0 || size_t(lds_cells) * 2 > 160 * 1024) return -1;
-  uint32_t grid = n;
-  if (max_groups && grid > max_groups) grid = max_groups;
-  const uint32_t win = window_bytes(grid, size_t(lds_cells) * 2, 0);
-  const size_t lds = win ? ((size_t(lds_cells) * 2 + 15) & ~size_t(15)) + win : size_t(lds_cells) * 2;
-  const void* kfn = win ? reinterpret_cast<const void*>(lzgpu_session_coop_kernel<true>)
-                        : reinterpret_cast<const void*>(lzgpu_session_coop_kernel<false>);
-  if (lds > 64 * 1024 && allow_full_lds(kfn) != 0) return -1;
-  if (win)
-    hipLaunchKernelGGL(lzgpu_session_coop_kernel<true>, dim3(grid), dim3(32), lds, stream, d_sess,
-                       n, lds_cells, win);
-  else
-    hipLaunchKernelGGL(lzgpu_session_coop_kernel<false>, dim3(grid), dim3(32), lds, stream,
-                       d_sess, n, lds_cells, 0u);
+  lzgpu_host::LaunchShape s;
+  if (!lzgpu_session_launch_shape(n, lds_cells, max_groups, 0, nullptr, &s)) return -1;
+  auto kfn = s.win_bytes ? lzgpu_session_coop_kernel<true> : lzgpu_session_coop_kernel<false>;
+  if (s.lds_bytes > 64 * 1024 && allow_full_lds(reinterpret_cast<const void*>(kfn)) != 0)
+    return -1;
+  hipLaunchKernelGGL(kfn, dim3(s.grid), dim3(s.block), s.lds_bytes, stream, d_sess, n, lds_cells,
+                     s.win_bytes);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -288,215 +277,78 @@ extern "C" int lzgpu_launch_decode_batch(const LzmaGpuStreamDesc* d_descs, const
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// One-stream waves on kLaneDup lanes (lzgpu_decode_dup_kernel): `groups_per_cu`
-// one-wave workgroups per CU, each padded to its share of the CU's LDS blocks.
-template <int W, uint32_t M, bool K2>
-static int launch_dup(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order, uint32_t n,
-                      const uint8_t* d_src, uint8_t* d_dst, uint16_t* d_ws,
-                      LzmaGpuResult* d_results, uint32_t stride, uint32_t groups_per_cu,
-                      uint32_t max_groups, uint32_t* d_queue, uint32_t dup, hipStream_t stream) {
-  auto kd = lzgpu_decode_dup_kernel<W, M, K2>;
-  if (allow_full_lds(reinterpret_cast<const void*>(kd)) != 0) return -1;
-  if (hipMemsetAsync(d_queue, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
-  size_t lds = size_t(stride) * 2;
-  if (groups_per_cu) lds = std::max(lds, lzgpu_host::lds_share(groups_per_cu));
-  uint32_t grid = n;
-  if (max_groups && grid > max_groups) grid = max_groups;
-  hipLaunchKernelGGL(kd, dim3(grid), dim3(dup), lds, stream, d_descs, d_order, n, d_src, d_dst,
-                     d_ws, d_results, stride, d_queue);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+// Every build of the three LDS decode kernels, by what decode_launch_shape
+// names it with: family, W, placement, K2.  The kernels of a family share one
+// signature whatever their template arguments.
+struct KernelRow {
+  uint32_t family, w, mask, k2;
+  const void* fn;
+};
+#define LZ_ROWS_W(F, K, W, M)                                      \
+  {F, W, M, 0u, reinterpret_cast<const void*>(K<W, M, false>)},    \
+      {F, W, M, 1u, reinterpret_cast<const void*>(K<W, M, true>)},
+#define LZ_ROWS_W24(F, K, M) LZ_ROWS_W(F, K, 2, M) LZ_ROWS_W(F, K, 4, M)
+#define LZ_ROWS_W124(F, K, M) LZ_ROWS_W(F, K, 1, M) LZ_ROWS_W24(F, K, M)
+static const KernelRow kDecodeKernels[] = {
+    LZ_ROWS_W124(lzgpu_host::kFamLds, lzgpu_decode_lds_kernel, LZGPU_LDS_MASK)
+    LZ_ROWS_W124(lzgpu_host::kFamLds, lzgpu_decode_lds_kernel, LZGPU_LDS_MASK | kIlvBit)
+    LZ_ROWS_W124(lzgpu_host::kFamLds, lzgpu_decode_lds_kernel, LZGPU_LDS_MASK_LAT)
+    LZ_ROWS_W124(lzgpu_host::kFamDup, lzgpu_decode_dup_kernel, LZGPU_LDS_MASK_LAT)
+    LZ_ROWS_W124(lzgpu_host::kFamDup, lzgpu_decode_dup_kernel, kLdsMaskLatSlotG)
+    // one wave per workgroup: W = 1 would not raise the register budget
+    LZ_ROWS_W24(lzgpu_host::kFamCoop, lzgpu_decode_coop_kernel, LZGPU_LDS_MASK_LAT | kCoopBit)
+    LZ_ROWS_W24(lzgpu_host::kFamCoop, lzgpu_decode_coop_kernel, LZGPU_LDS_MASK_ALL | kCoopBit)
+    LZ_ROWS_W24(lzgpu_host::kFamCoop, lzgpu_decode_coop_kernel,
+                LZGPU_LDS_MASK_ALL | kCoopBit | kWinBit)};
+#undef LZ_ROWS_W124
+#undef LZ_ROWS_W24
+#undef LZ_ROWS_W
+
+using LdsKernel = decltype(&lzgpu_decode_lds_kernel<1, LZGPU_LDS_MASK, false>);
+using DupKernel = decltype(&lzgpu_decode_dup_kernel<1, LZGPU_LDS_MASK_LAT, false>);
+using CoopKernel = decltype(&lzgpu_decode_coop_kernel<2, LZGPU_LDS_MASK_LAT | kCoopBit, false>);
+
+extern "C" uint32_t lzgpu_decode_kernel_rows(uint32_t* rows, uint32_t cap) {
+  uint32_t k = 0;
+  for (const KernelRow& r : kDecodeKernels) {
+    if (k < cap) memcpy(rows + 4 * k, &r, 4 * sizeof(uint32_t));  // family, w, mask, k2
+    ++k;
+  }
+  return k;
 }
 
-// kLaneDup, or LZGPU_DUP=D for A/B (D = 1 launches the one-lane kernel)
-static int lane_dup() {
-  static const int dup = [] {
-    const char* e = getenv("LZGPU_DUP");
-    return e ? atoi(e) : kLaneDup;
-  }();
-  return dup;
+extern "C" int lzgpu_decode_launch_shape(const LzmaGpuLdsClass* c, uint32_t n, uint32_t max_groups,
+                                         uint32_t cus, const lzgpu_host::LaunchEnv* env,
+                                         lzgpu_host::LaunchShape* out) {
+  return lzgpu_host::decode_launch_shape(*c, n, max_groups, cus ? cus : lzgpu_host::device_cus(),
+                                         env ? *env : launch_env(), *out);
 }
 
-template <int W, uint32_t M, bool K2>
-static int launch_lds(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order, uint32_t n,
-                      const uint8_t* d_src, uint8_t* d_dst, uint16_t* d_ws,
-                      LzmaGpuResult* d_results, uint32_t lanes, uint32_t stride,
-                      uint32_t groups_per_cu, uint32_t max_groups, uint32_t* d_queue,
-                      const LzgpuSlots& sl, hipStream_t stream) {
-  if (allow_full_lds(reinterpret_cast<const void*>(lzgpu_decode_lds_kernel<W, M, K2>)) != 0)
-    return -1;
-  if (hipMemsetAsync(d_queue, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
-  // pad each workgroup's LDS so that exactly groups_per_cu fit on a CU (an
-  // even split over its four SIMDs), whatever the dispatcher would pack;
-  // interleaved slices take whole 32-lane rows
-  size_t lds = size_t(lds_ilv<M>() ? (lanes + kIlv - 1) / kIlv * kIlv : lanes) * stride * 2;
-  if (groups_per_cu) {
-    const size_t share = lzgpu_host::lds_share(groups_per_cu);
-    if (share > lds) lds = share;
-  }
-  uint32_t grid = (n + lanes - 1) / lanes;
-  if (max_groups && grid > max_groups) grid = max_groups;
-  if constexpr ((M & kIlvBit) != 0u) {
-    // the slot area holds sl.groups workgroups' columns; persistent lanes
-    // cover the rest of the batch from the queue
-    if (sl.groups == 0 || lanes > 64) return -1;
-    if (grid > sl.groups) {
-      if (!max_groups) return -1;
-      grid = sl.groups;
-    }
-  }
-  const uint32_t lanes_total = grid * lanes;
-  if constexpr (M == LZGPU_LDS_MASK_LAT) {
-    // one-stream waves: kLaneDup lanes per stream
-    const int dup = lane_dup();
-    if (lanes == 1 && dup > 1 && dup <= 64) {
-      auto kd = lzgpu_decode_dup_kernel<W, M, K2>;
-      if (allow_full_lds(reinterpret_cast<const void*>(kd)) != 0) return -1;
-      hipLaunchKernelGGL(kd, dim3(grid), dim3(dup), lds, stream, d_descs, d_order, n, d_src, d_dst,
-                         d_ws, d_results, stride, d_queue);
-      return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-  }
-  auto kfn = lzgpu_decode_lds_kernel<W, M, K2>;
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(lanes), lds, stream, d_descs, d_order, n, d_src, d_dst,
-                     d_ws, d_results, stride, d_queue, sl.off, sl.cells, lanes_total);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// MW: the same placement with the LDS history window, launched instead when
-// the launch leaves room for one (window_bytes); 0 = no window build.
-template <int W, uint32_t M, bool K2, uint32_t MW = 0u>
-static int launch_coop(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order, uint32_t n,
-                       const uint8_t* d_src, uint8_t* d_dst, uint16_t* d_ws,
-                       LzmaGpuResult* d_results, uint32_t stride, uint32_t groups_per_cu,
-                       uint32_t max_groups, uint32_t* d_queue, hipStream_t stream) {
-  uint32_t grid = n;
-  if (max_groups && grid > max_groups) grid = max_groups;
-  const uint32_t win = MW ? window_bytes(grid, size_t(stride) * 2, groups_per_cu) : 0u;
-  auto kfn = win ? lzgpu_decode_coop_kernel<W, (MW ? MW : M), K2> : lzgpu_decode_coop_kernel<W, M, K2>;
-  if (allow_full_lds(reinterpret_cast<const void*>(kfn)) != 0) return -1;
-  if (hipMemsetAsync(d_queue, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
-  size_t lds = size_t(stride) * 2;
-  if (win) {
-    lds = ((lds + 15) & ~size_t(15)) + win;
-  } else if (groups_per_cu) {
-    const size_t share = lzgpu_host::lds_share(groups_per_cu);
-    if (share > lds) lds = share;
-  }
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(32), lds, stream, d_descs, d_order, n, d_src, d_dst,
-                     d_ws, d_results, stride, d_queue, win);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-template <uint32_t M, bool K2>
-static int launch_lds_w(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order, uint32_t n,
-                        const uint8_t* d_src, uint8_t* d_dst, uint16_t* d_ws,
-                        LzmaGpuResult* d_results, uint32_t lanes, uint32_t stride,
-                        uint32_t waves_per_simd, uint32_t groups_per_cu, uint32_t max_groups,
-                        uint32_t* d_queue, const LzgpuSlots& sl, hipStream_t stream) {
-  if (waves_per_simd <= 1)
-    return launch_lds<1, M, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes, stride,
-                                groups_per_cu, max_groups, d_queue, sl, stream);
-  if (waves_per_simd == 2)
-    return launch_lds<2, M, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes, stride,
-                                groups_per_cu, max_groups, d_queue, sl, stream);
-  return launch_lds<4, M, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes, stride,
-                              groups_per_cu, max_groups, d_queue, sl, stream);
-}
-
-// Workgroups a CU actually holds at once: the launch's workgroups spread over
-// the CUs, so at most min(groups_per_cu, ceil(n / cus)).  The register budget
-// (the W of __launch_bounds__) follows it: a plan for 16 narrow-table
-// cooperative waves per CU that gets one stream (a lone drop-in call) would
-// otherwise run the W = 4 build, 128 VGPRs and 46-218 spilled, instead of the
-// W = 2 build without spills.
-static uint32_t resident_waves_per_simd(uint32_t n, uint32_t groups_per_cu) {
-  const uint32_t cus = std::max(1u, lzgpu_host::device_cus());
-  const uint32_t per_cu = std::max(1u, std::min(groups_per_cu, (n + cus - 1) / cus));
-  return (per_cu + 3) / 4;
-}
-
-template <bool K2>
-static int launch_class(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order, uint32_t n,
-                        const uint8_t* d_src, uint8_t* d_dst, uint16_t* d_ws,
-                        LzmaGpuResult* d_results, uint32_t lanes, uint32_t stride,
-                        uint32_t waves_per_simd, uint32_t groups_per_cu, uint32_t max_groups,
-                        uint32_t* d_queue, uint32_t lds_mask, const LzgpuSlots& sl,
-                        hipStream_t stream, uint32_t class_flags) {
-  if (lds_mask == LZGPU_LDS_MASK)
-    return launch_lds_w<LZGPU_LDS_MASK, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results,
-                                            lanes, stride, waves_per_simd, groups_per_cu,
-                                            max_groups, d_queue, sl, stream);
-  if (lds_mask == (LZGPU_LDS_MASK | kIlvBit))
-    return launch_lds_w<LZGPU_LDS_MASK | kIlvBit, K2>(d_descs, d_order, n, d_src, d_dst, d_ws,
-                                                      d_results, lanes, stride, waves_per_simd,
-                                                      groups_per_cu, max_groups, d_queue, sl,
-                                                      stream);
-  if (lds_mask == (LZGPU_LDS_MASK_LAT | kCoopBit)) {
-    // one wave per workgroup: register budget by workgroups per SIMD
-    constexpr uint32_t MC = LZGPU_LDS_MASK_LAT | kCoopBit;
-    const uint32_t w = resident_waves_per_simd(n, groups_per_cu);
-    if (w <= 2)
-      return launch_coop<2, MC, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, stride,
-                                    groups_per_cu, max_groups, d_queue, stream);
-    return launch_coop<4, MC, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, stride,
-                                  groups_per_cu, max_groups, d_queue, stream);
-  }
-  if (lds_mask == (LZGPU_LDS_MASK_ALL | kCoopBit)) {
-    // the whole table in LDS, plus the history window where the launch has room
-    constexpr uint32_t MC = LZGPU_LDS_MASK_ALL | kCoopBit;
-    const uint32_t w = resident_waves_per_simd(n, groups_per_cu);
-    if (w <= 2)
-      return launch_coop<2, MC, K2, MC | kWinBit>(d_descs, d_order, n, d_src, d_dst, d_ws,
-                                                  d_results, stride, groups_per_cu, max_groups,
-                                                  d_queue, stream);
-    return launch_coop<4, MC, K2, MC | kWinBit>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results,
-                                                stride, groups_per_cu, max_groups, d_queue,
-                                                stream);
-  }
-  if (lds_mask == kLdsMaskLatSlotG) {
-    // planned for one-stream workgroups only (lzma_capi.hip plan_bucket)
-    const int dup = lane_dup();
-    if (lanes != 1 || dup <= 1 || dup > 64) return -1;
-    const uint32_t w = std::min(waves_per_simd, resident_waves_per_simd(n, groups_per_cu));
-    if (w <= 1)
-      return launch_dup<1, kLdsMaskLatSlotG, K2>(d_descs, d_order, n, d_src, d_dst, d_ws,
-                                                 d_results, stride, groups_per_cu, max_groups,
-                                                 d_queue, uint32_t(dup), stream);
-    if (w == 2)
-      return launch_dup<2, kLdsMaskLatSlotG, K2>(d_descs, d_order, n, d_src, d_dst, d_ws,
-                                                 d_results, stride, groups_per_cu, max_groups,
-                                                 d_queue, uint32_t(dup), stream);
-    return launch_dup<4, kLdsMaskLatSlotG, K2>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results,
-                                               stride, groups_per_cu, max_groups, d_queue,
-                                               uint32_t(dup), stream);
-  }
-  if (lds_mask == LZGPU_LDS_MASK_LAT)
-    return launch_lds_w<LZGPU_LDS_MASK_LAT, K2>(d_descs, d_order, n, d_src, d_dst, d_ws,
-                                                d_results, lanes, stride,
-                                                lanes == 1 ? std::min(waves_per_simd,
-                                                                      resident_waves_per_simd(
-                                                                          n, groups_per_cu))
-                                                           : waves_per_simd,
-                                                groups_per_cu, max_groups, d_queue, sl, stream);
-  return -1;  // no kernel built for this placement
-}
-
-extern "C" int lzgpu_launch_decode_lds(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_order,
-                                       uint32_t n, const uint8_t* d_src, uint8_t* d_dst,
-                                       uint16_t* d_ws, LzmaGpuResult* d_results, uint32_t lanes,
-                                       uint32_t stride, uint32_t waves_per_simd,
-                                       uint32_t groups_per_cu, uint32_t max_groups,
-                                       uint32_t* d_queue, uint32_t lds_mask,
-                                       uint32_t class_flags, LzgpuSlots slots,
-                                       hipStream_t stream) {
+extern "C" int lzgpu_launch_decode_lds(const LzmaGpuLdsClass& c, const LzgpuDecodeBufs& b,
+                                       uint32_t max_groups, hipStream_t stream) {
+  const uint32_t n = uint32_t(c.n);
   if (n == 0) return 0;
-  if (class_flags & LZMA_GPU_CLASS_HAS_LZMA2)
-    return launch_class<true>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes, stride,
-                              waves_per_simd, groups_per_cu, max_groups, d_queue, lds_mask,
-                              slots, stream, class_flags);
-  return launch_class<false>(d_descs, d_order, n, d_src, d_dst, d_ws, d_results, lanes, stride,
-                             waves_per_simd, groups_per_cu, max_groups, d_queue, lds_mask, slots,
-                             stream, class_flags);
+  lzgpu_host::LaunchShape s;
+  if (!lzgpu_decode_launch_shape(&c, n, max_groups, 0, nullptr, &s)) return -1;
+  const void* fn = nullptr;
+  for (const KernelRow& r : kDecodeKernels)
+    if (r.family == s.family && r.w == s.w && r.mask == s.mask && r.k2 == s.k2) fn = r.fn;
+  if (!fn) return -1;  // no kernel built for this placement
+  if (allow_full_lds(fn) != 0) return -1;
+  if (hipMemsetAsync(b.queue, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
+  const dim3 grid(s.grid), block(s.block);
+  const uint32_t stride = c.lds_cells_per_lane;
+  if (s.family == lzgpu_host::kFamLds)
+    hipLaunchKernelGGL(LdsKernel(fn), grid, block, s.lds_bytes, stream, b.descs, b.order, n, b.src,
+                       b.dst, b.ws, b.results, stride, b.queue, c.slot_off, c.slot_cells,
+                       s.lanes_total);
+  else if (s.family == lzgpu_host::kFamDup)
+    hipLaunchKernelGGL(DupKernel(fn), grid, block, s.lds_bytes, stream, b.descs, b.order, n, b.src,
+                       b.dst, b.ws, b.results, stride, b.queue);
+  else
+    hipLaunchKernelGGL(CoopKernel(fn), grid, block, s.lds_bytes, stream, b.descs, b.order, n,
+                       b.src, b.dst, b.ws, b.results, stride, b.queue, s.win_bytes);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 extern "C" int lzgpu_launch_session(LzgpuSession* d_sess, uint32_t n, hipStream_t stream) {
