@@ -662,6 +662,58 @@ int Bcj2_Decode(const Byte *buf0, SizeT size0, const Byte *buf1, SizeT size1, co
                 SizeT size2, const Byte *buf3, SizeT size3, Byte *outBuf, SizeT outSize);
 SRes Bcj2Gpu_Batch(const Bcj2GpuJob *d_jobs, size_t n, int32_t *d_res, void *stream);
 
+/* The BCJ2 encoder (the reference ships none; csrc/bcj2enc_device.h states the
+ * rule): stream i's src_len bytes split into the four streams that Bcj2_Decode
+ * merges -- out[0] main, out[1] CALL targets, out[2] JMP / Jcc targets, out[3]
+ * the range-coded bits -- a branch being converted when its absolute target
+ * lies inside the stream's own bytes.  The split is computed in parallel over
+ * positions (a large stream spreads over the chip, small streams share
+ * workgroups); only the range coder is one lane per stream, one step per branch
+ * opcode.  Per stream:
+ *   SZ_OK                 len[k] bytes written at out[k].off
+ *   SZ_ERROR_OUTPUT_EOF   a stream outgrew its cap: len[] holds the four true
+ *                         lengths; nothing is written at or past a cap (a
+ *                         target is written whole or not at all)
+ *   SZ_ERROR_UNSUPPORTED  src_len >= 2^31; nothing read or written
+ * Bcj2EncGpu_Bound: capacities that hold whatever the data (n, 4 (n / 5),
+ * 4 (n / 5), 5 + n). */
+typedef struct Bcj2GpuEncRange {
+  uint64_t off, cap;          /* in d_dst */
+} Bcj2GpuEncRange;
+typedef struct Bcj2GpuEncDesc {   /* 80 bytes */
+  uint64_t src_off, src_len;  /* in d_src; any byte alignment */
+  Bcj2GpuEncRange out[4];     /* main, call, jump, rc */
+} Bcj2GpuEncDesc;
+typedef struct Bcj2GpuEncResult { /* 40 bytes */
+  int32_t res;
+  uint32_t _pad;
+  uint64_t len[4];            /* main, call, jump, rc */
+} Bcj2GpuEncResult;
+#define LZMA_GPU_BCJ2_MAIN 0
+#define LZMA_GPU_BCJ2_CALL 1
+#define LZMA_GPU_BCJ2_JUMP 2
+#define LZMA_GPU_BCJ2_RC 3
+/* Host only. */
+void Bcj2EncGpu_Bound(uint64_t src_len, uint64_t bound[4]);
+/* Host only: the bytes of scratch a batch of these descriptors needs (a fixed
+ * part plus a slice per stream of about 2 src_len); 16-byte aligned memory. */
+uint64_t Bcj2EncGpu_Scratch(const Bcj2GpuEncDesc *descs, size_t n);
+/* All pointers device memory, the scratch uninitialised; asynchronous on
+ * `stream`; n == 0 is a no-op.  SZ_OK if the launches were queued
+ * (SZ_ERROR_PARAM for n above 2^31 - 1, SZ_ERROR_FAIL without a device);
+ * per-stream outcomes land in d_results. */
+SRes Bcj2EncGpu_EncodeBatch(const Bcj2GpuEncDesc *d_descs, size_t n, const Byte *d_src,
+                            Byte *d_dst, void *d_scratch, Bcj2GpuEncResult *d_results,
+                            void *stream);
+/* The same over host buffers, in as many launches as keep the scratch at or
+ * under workspace_limit bytes (0 = half of the device's free memory).
+ * SZ_ERROR_MEM if one stream's scratch alone exceeds the limit or an allocation
+ * fails, SZ_ERROR_PARAM for a range outside src / dst, SZ_ERROR_FAIL without a
+ * device. */
+SRes Bcj2EncGpu_EncodeBatchHost(const Bcj2GpuEncDesc *descs, size_t n, const Byte *src,
+                                size_t src_size, Byte *dst, size_t dst_size,
+                                Bcj2GpuEncResult *results, uint64_t workspace_limit);
+
 /* CRC-64 (XzCrc64.c, poly 0xC96C5795D7870F42).  Crc64Calc drop-in replaces
  * XzCrc64.h:20 / XzCrc64.c:30 (host buffer, GPU compute; 0 without a device).
  * The batch form mirrors CrcGpu_Batch with 2048-byte chunks planned by
@@ -1190,8 +1242,19 @@ SRes LzmaGpu_7zExtractEx(Byte *dest, SizeT *destLen, const Byte *archive, size_t
  * PPMd7 without end mark (props: order, memSize LE32), Copy the bytes.  Every
  * data file's CRC-32 is in SubStreamsInfo; no folder CRCs (except the packed
  * header's); no times, no attributes: the archive is a function of its inputs.
- * Not written: the optimal parser (levels 5+), BCJ2 folders, times and
- * attributes, an archive that does not fit in device memory at once. */
+ * A BCJ2 folder (filter LZMA_GPU_7Z_FILTER_BCJ2 on an LZMA row) has the one
+ * layout CheckSupportedFolder accepts (7zDec.c:303-319): coders 0, 1, 2 = the
+ * JMP, CALL and main streams as LZMA, coder 3 = BCJ2 (0x0303011B, 4 in, 1 out),
+ * bind pairs 5<-0, 4<-1, 3<-2, pack streams 2, 6, 1, 0 = the main LZMA stream,
+ * the raw rc stream, the CALL and the JMP LZMA streams.  The main coder has the
+ * row's props; the CALL and JMP coders the row's with lc 0, lp 2, pb 2 and the
+ * dictionary min(the row's normalised dictSize, 1 MiB).  A branch is converted
+ * when its target lies inside the folder's data (a JOIN group: the whole
+ * group).  The split (Bcj2EncGpu_EncodeBatch's kernels) is out of place, so a
+ * BCJ2 folder's source range may overlap another folder's.
+ * Not written: the optimal parser (levels 5+), BCJ2 over LZMA2, PPMd7 or Copy
+ * rows, times and attributes, an archive that does not fit in device memory at
+ * once. */
 
 #define LZMA_GPU_7Z_ITEM_DIR 1u   /* a directory: size must be 0 */
 #define LZMA_GPU_7Z_ITEM_JOIN 2u  /* continues the folder of the previous data item (solid) */
@@ -1211,9 +1274,12 @@ typedef struct LzmaGpu7zItem {     /* 32 bytes */
 /* One row of the method table.  method: 0 Copy, 0x030101 LZMA (props.lzmaProps),
  * 0x21 LZMA2 (props, blockSize after Lzma2EncProps_Normalize cuts the folder),
  * 0x030401 PPMd7 (ppmd_order 2..64, ppmd_mem_size 1<<11 .. 0xFFFFFFFF-36);
- * filter: 0 none, 4 x86, 7 ARM (the xz ids of BraGpu_Batch).  The props go
+ * filter: 0 none, 4 x86, 7 ARM (the xz ids of BraGpu_Batch), 0x1B BCJ2 (LZMA
+ * rows only: SZ_ERROR_UNSUPPORTED on another row; any other value
+ * SZ_ERROR_PARAM).  The props go
  * through LzmaEncGpu_DescFromProps / Lzma2EncGpu_DescFromProps: their
  * SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED (level 5 and up) stand. */
+#define LZMA_GPU_7Z_FILTER_BCJ2 0x1Bu
 typedef struct LzmaGpu7zMethod {   /* 88 bytes */
   uint64_t method;
   uint32_t filter;
@@ -1258,7 +1324,8 @@ typedef struct LzmaGpu7zWriteStats {     /* 112 bytes */
  * bad JOIN, more than 2^32 - 2 items; SZ_ERROR_UNSUPPORTED for an LZMA or PPMd7
  * folder of 2^31 bytes or more.  Fills up to folder_cap folders (folders may be
  * NULL): unpack_size, dst_off (the folder's start in the source), method, x86,
- * num_coders (2 with a filter; x86 == 0 then means ARM), props / props_size,
+ * num_coders (2 with a filter; x86 == 0 then means ARM; 4 for a BCJ2 folder,
+ * which counts four pieces), props / props_size,
  * first_file (index of the folder's first item), num_files; pack_off, pack_size,
  * crc_defined, crc are 0.  *n_pieces: encode pieces + Copy ranges.
  * *dest_bound: a dest of that many bytes holds the archive whatever the data
@@ -1285,9 +1352,29 @@ SRes LzmaGpu_7zWriteHeader(const LzmaGpu7zFolder *folders, size_t n_folders,
                            size_t header_cap, size_t *header_len, Byte *sig32,
                            uint64_t pack_area_size);
 
+/* What the header needs beside LzmaGpu7zFolder for a four-coder (BCJ2) folder. */
+typedef struct LzmaGpu7zBcj2Info {   /* 72 bytes */
+  uint64_t pack_size[4];     /* main, rc, call, jump: the folder's pack streams in order */
+  uint64_t unpack_size[3];   /* coders 0, 1, 2: the jump, call and main streams */
+  Byte call_props[5], jump_props[5];
+  Byte reserved[6];          /* 0 */
+} LzmaGpu7zBcj2Info;
+/* LzmaGpu_7zWriteHeader with bcj2[k] for the k-th folder of num_coders == 4, in
+ * order (its pack_size is not read); fewer entries than such folders:
+ * SZ_ERROR_PARAM.  LzmaGpu_7zWriteHeader is this call with no entries. */
+SRes LzmaGpu_7zWriteHeaderEx(const LzmaGpu7zFolder *folders, size_t n_folders,
+                             const LzmaGpu7zItem *items, size_t n, const uint32_t *file_crcs,
+                             const UInt16 *names, size_t names_len, unsigned flags,
+                             const LzmaGpu7zBcj2Info *bcj2, size_t n_bcj2, Byte *header,
+                             size_t header_cap, size_t *header_len, Byte *sig32,
+                             uint64_t pack_area_size);
+
 /* The whole archive from host memory: upload, CRC batch, filter batches (in
  * place, after the CRCs; a filtered folder's source range may not overlap
- * another folder's: SZ_ERROR_PARAM), the LZMA, LZMA2 and PPMd7 batches (each cut
+ * another folder's: SZ_ERROR_PARAM; the BCJ2 split writes its four streams behind
+ * the uploaded source and its lengths come back in one small copy; its three
+ * LZMA streams per folder join the LZMA batch and rc is a Copy piece), the LZMA,
+ * LZMA2 and PPMd7 batches (each cut
  * by workspace_limit as the *BatchHost calls are), pack, one download of the
  * pack area and one of the pack sizes, header.  LZMA and PPMd7 have no tight
  * bound: a stream gets a slot of len + len / 128 + 64 bytes first (incompressible

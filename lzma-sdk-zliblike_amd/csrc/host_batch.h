@@ -95,6 +95,15 @@ std::vector<Desc> in_caller_order(const Desc* descs, const LaunchPlan& p) {
   return d;
 }
 
+// for descriptors that carry no workspace offset (the kernels lay a launch's
+// scratch out themselves): launch order only
+template <class Desc>
+std::vector<Desc> in_plan_order(const Desc* descs, const LaunchPlan& p) {
+  std::vector<Desc> d(p.order.size());
+  for (size_t k = 0; k < d.size(); ++k) d[k] = descs[p.order[k]];
+  return d;
+}
+
 // launch(lo, cnt) once per cut of the plan; it picks its own pointers and
 // returns 0 on success
 template <class Launch>
@@ -119,6 +128,7 @@ struct HostBatch {
   DevArr<Desc> desc;
   DevArr<Res> res;
   DevArr<uint32_t> order;  // only with descriptors in caller order
+  uint64_t ws_fixed = 0;   // workspace bytes of a launch beside its streams' slices
 
   // What is checked before anything is allocated: every range lies in its
   // buffer (dst_bytes(d): the stream's range in dst), and the layout of the
@@ -127,16 +137,27 @@ struct HostBatch {
   template <class DstBytes, class Work, class Slice>
   SRes lay_out(const char* what, const Desc* descs, size_t n, size_t src_size, size_t dst_size,
                uint64_t limit, DstBytes dst_bytes, Work work, Slice slice) {
+    return lay_out_ranges(
+        what, descs, n, limit,
+        [&](const Desc& d) {
+          return d.src_off <= src_size && d.src_len <= src_size - d.src_off &&
+                 d.dst_off <= dst_size && dst_bytes(d) <= dst_size - d.dst_off;
+        },
+        work, slice);
+  }
+  // lay_out with the caller's own range check (in_range(d): every range of the
+  // stream lies in its buffer)
+  template <class InRange, class Work, class Slice>
+  SRes lay_out_ranges(const char* what, const Desc* descs, size_t n, uint64_t limit,
+                      InRange in_range, Work work, Slice slice) {
     if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-    for (size_t i = 0; i < n; ++i) {
-      const Desc& d = descs[i];
-      if (d.src_off > src_size || d.src_len > src_size - d.src_off || d.dst_off > dst_size ||
-          dst_bytes(d) > dst_size - d.dst_off)
-        return SZ_ERROR_PARAM;
-    }
+    for (size_t i = 0; i < n; ++i)
+      if (!in_range(descs[i])) return SZ_ERROR_PARAM;
     if (!default_workspace_limit(limit)) return SZ_ERROR_FAIL;
+    // the launches' slices share the limit with the fixed part
     if (!launch_plan(n, [&](uint32_t i) { return work(descs[i]); },
-                     [&](uint32_t i) { return slice(descs[i]); }, limit, plan)) {
+                     [&](uint32_t i) { return slice(descs[i]); },
+                     limit > ws_fixed ? limit - ws_fixed : 0, plan)) {
       set_error((std::string(what) + ": one stream's workspace slice exceeds the limit").c_str());
       return SZ_ERROR_MEM;
     }
@@ -152,7 +173,8 @@ struct HostBatch {
              size_t src_size, const Byte* dst_init, size_t dst_size, Launch launch) {
     const size_t n = d.size();
     SRes r =
-        alloc_all(what, src, src_size, dst, dst_size, ws, size_t(plan.ws_max), desc, n, res, n);
+        alloc_all(what, src, src_size, dst, dst_size, ws, size_t(plan.ws_max + ws_fixed), desc, n,
+                  res, n);
     if (r == SZ_OK && with_order) r = alloc_all(what, order, n);
     if (r != SZ_OK) return r;
     if (!hip_ok(hipMemcpy(src.p, src_host, src_size, hipMemcpyHostToDevice), "upload src") ||

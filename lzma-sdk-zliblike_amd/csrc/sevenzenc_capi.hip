@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
+#include "bcj2enc_device.h"
+#include "bcj2enc_internal.h"
 #include "host_batch.h"
 #include "lzma2enc_internal.h"
 #include "lzma_gpu_internal.h"
@@ -23,14 +25,16 @@ using namespace lzgpu_host;
 
 static_assert(sizeof(LzmaGpu7zItem) == 32 && sizeof(LzmaGpu7zMethod) == 88 &&
                   sizeof(LzmaGpu7zWriteOptions) == 16 && sizeof(LzmaGpu7zWriteStats) == 112 &&
-                  sizeof(SzGpuPackPiece) == 32 && sizeof(SzGpuPackArgs) == 152,
+                  sizeof(SzGpuPackPiece) == 32 && sizeof(SzGpuPackArgs) == 152 &&
+                  sizeof(LzmaGpu7zBcj2Info) == 72,
               "7z writer ABI");
 
 namespace {
 
 constexpr uint64_t kCopy = 0, kLzma = 0x030101, kLzma2 = 0x21, kPpmd = 0x030401;
 constexpr uint64_t kBcjX86 = 0x03030103, kBcjArm = 0x03030501;
-constexpr uint32_t kFilterX86 = 4, kFilterArm = 7;
+constexpr uint64_t kBcj2 = 0x0303011B;
+constexpr uint32_t kFilterX86 = 4, kFilterArm = 7, kFilterBcj2 = LZMA_GPU_7Z_FILTER_BCJ2;
 // 7z.h:17-45
 constexpr uint8_t kEnd = 0, kHeader = 1, kMainStreamsInfo = 4, kFilesInfo = 5, kPackInfo = 6,
                   kUnpackInfo = 7, kSubStreamsInfo = 8, kSize = 9, kCrc = 10, kFolder = 11,
@@ -61,6 +65,8 @@ struct Method {
   uint32_t order = 0, mem = 0;  // PPMd7
   uint8_t props[5] = {0, 0, 0, 0, 0};
   uint32_t props_size = 0;
+  LzmaEncGpuStreamDesc target_proto;  // BCJ2: the CALL and JMP coders
+  uint8_t target_props[5] = {0, 0, 0, 0, 0};
 };
 
 struct FolderPlan {
@@ -72,18 +78,34 @@ struct FolderPlan {
 struct Plan {
   std::vector<Method> methods;
   std::vector<FolderPlan> folders;
-  uint64_t n_data = 0, n_pieces = 0, pack_bound = 0;
+  uint64_t n_data = 0, n_pieces = 0, pack_bound = 0, n_bcj2 = 0;
 };
 
 SRes resolve_method(const LzmaGpu7zMethod& in, Method& m) {
   memset(&m.proto, 0, sizeof(m.proto));
   m.id = in.method;
   m.filter = in.filter;
-  if (in.filter != 0 && in.filter != kFilterX86 && in.filter != kFilterArm) return SZ_ERROR_PARAM;
+  if (in.filter != 0 && in.filter != kFilterX86 && in.filter != kFilterArm &&
+      in.filter != kFilterBcj2)
+    return SZ_ERROR_PARAM;
+  if (in.filter == kFilterBcj2 && (in.method == kCopy || in.method == kLzma2 || in.method == kPpmd)) {
+    set_error("7z write: the BCJ2 filter is written over LZMA rows only");
+    return SZ_ERROR_UNSUPPORTED;
+  }
   if (in.method == kCopy) return SZ_OK;
   if (in.method == kLzma) {
     m.props_size = 5;
-    return LzmaEncGpu_DescFromProps(&in.props.lzmaProps, 0, &m.proto, m.props);
+    const SRes r = LzmaEncGpu_DescFromProps(&in.props.lzmaProps, 0, &m.proto, m.props);
+    if (r != SZ_OK || in.filter != kFilterBcj2) return r;
+    // the CALL and JMP coders: lc 0, lp 2, pb 2, a dictionary of at most 1 MiB
+    CLzmaEncProps t = in.props.lzmaProps;
+    LzmaEncProps_Normalize(&t);
+    t.lc = 0;
+    t.lp = 2;
+    t.pb = 2;
+    if (t.dictSize > (1u << 20)) t.dictSize = 1u << 20;
+    memset(&m.target_proto, 0, sizeof(m.target_proto));
+    return LzmaEncGpu_DescFromProps(&t, 0, &m.target_proto, m.target_props);
   }
   if (in.method == kLzma2) {
     m.props_size = 1;
@@ -167,6 +189,16 @@ SRes make_plan(const LzmaGpu7zItem* items, size_t n, size_t src_size, size_t nam
         set_error("7z write: an LZMA or PPMd7 folder of 2^31 bytes or more is not supported");
         return SZ_ERROR_UNSUPPORTED;
       }
+      if (m.filter == kFilterBcj2) {  // main, rc, call, jump
+        uint64_t b[4];
+        Bcj2EncGpu_Bound(f.size, b);
+        ++p.n_bcj2;
+        p.n_pieces += 4;
+        p.pack_bound += lzma_retry_slot(b[0], kReencodeRounds) + b[3] +
+                        lzma_retry_slot(b[1], kReencodeRounds) +
+                        lzma_retry_slot(b[2], kReencodeRounds);
+        continue;
+      }
       p.n_pieces += 1;
       p.pack_bound += lzma_retry_slot(f.size, kReencodeRounds);
     }
@@ -188,13 +220,14 @@ void fill_folder(const Plan& p, size_t k, LzmaGpu7zFolder& o) {
   o.x86 = m.filter == kFilterX86 ? 1 : 0;
   o.first_file = f.first_item;
   o.num_files = f.num_files;
-  o.num_coders = m.filter ? 2 : 1;
+  o.num_coders = m.filter == kFilterBcj2 ? 4 : (m.filter ? 2 : 1);
   o.props_size = m.props_size;
   memcpy(o.props, m.props, m.props_size);
 }
 
-uint64_t header_bound(size_t n_folders, size_t n_items, size_t names_len) {
-  return 64 + uint64_t(n_folders) * 64 + uint64_t(n_items) * 15 + uint64_t(names_len) * 2;
+uint64_t header_bound(size_t n_folders, size_t n_bcj2, size_t n_items, size_t names_len) {
+  return 64 + uint64_t(n_folders) * 64 + uint64_t(n_bcj2) * 128 + uint64_t(n_items) * 15 +
+         uint64_t(names_len) * 2;
 }
 
 // ---------------------------------------------------------------- the header
@@ -241,19 +274,45 @@ struct DataFile {
   uint32_t crc;
 };
 void put_streams_info(Bytes& o, const LzmaGpu7zFolder* folders, size_t nf, uint64_t pack_pos,
-                      const std::vector<DataFile>* files) {
+                      const std::vector<DataFile>* files, const LzmaGpu7zBcj2Info* bcj2 = nullptr) {
+  size_t n_four = 0;
+  for (size_t k = 0; k < nf; ++k) n_four += folders[k].num_coders == 4;
   o.push_back(kPackInfo);
   put_number(o, pack_pos);
-  put_number(o, nf);
+  put_number(o, nf + 3 * n_four);
   o.push_back(kSize);
-  for (size_t k = 0; k < nf; ++k) put_number(o, folders[k].pack_size);
+  for (size_t k = 0, b = 0; k < nf; ++k) {
+    if (folders[k].num_coders == 4) {
+      for (int j = 0; j < 4; ++j) put_number(o, bcj2[b].pack_size[j]);
+      ++b;
+    } else {
+      put_number(o, folders[k].pack_size);
+    }
+  }
   o.push_back(kEnd);
   o.push_back(kUnpackInfo);
   o.push_back(kFolder);
   put_number(o, nf);
   o.push_back(0);  // external
-  for (size_t k = 0; k < nf; ++k) {
+  for (size_t k = 0, b = 0; k < nf; ++k) {
     const LzmaGpu7zFolder& f = folders[k];
+    if (f.num_coders == 4) {
+      // coders 0, 1, 2 = jump, call, main; coder 3 = BCJ2 with 4 in, 1 out; bind
+      // pairs in <- out; the pack streams' in indices (7zDec.c:303-319)
+      const LzmaGpu7zBcj2Info& i = bcj2[b++];
+      put_number(o, 4);
+      put_coder(o, kLzma, i.jump_props, 5);
+      put_coder(o, kLzma, i.call_props, 5);
+      put_coder(o, f.method, f.props, f.props_size);
+      o.push_back(uint8_t(4 | 0x10));
+      for (unsigned j = 4; j-- > 0;) o.push_back(uint8_t(kBcj2 >> (8 * j)));
+      put_number(o, 4);
+      put_number(o, 1);
+      static const uint8_t kBind[6] = {5, 0, 4, 1, 3, 2}, kPack[4] = {2, 6, 1, 0};
+      for (uint8_t v : kBind) put_number(o, v);
+      for (uint8_t v : kPack) put_number(o, v);
+      continue;
+    }
     put_number(o, f.num_coders == 2 ? 2 : 1);
     put_coder(o, f.method, f.props, f.props_size);
     if (f.num_coders == 2) {  // coder 1 = the filter; bind pair: in 1 <- out 0
@@ -264,7 +323,11 @@ void put_streams_info(Bytes& o, const LzmaGpu7zFolder* folders, size_t nf, uint6
   }
   o.push_back(kCodersUnpackSize);
   bool any_crc = false;
-  for (size_t k = 0; k < nf; ++k) {
+  for (size_t k = 0, b = 0; k < nf; ++k) {
+    if (folders[k].num_coders == 4) {
+      for (int j = 0; j < 3; ++j) put_number(o, bcj2[b].unpack_size[j]);
+      ++b;
+    }
     put_number(o, folders[k].unpack_size);
     if (folders[k].num_coders == 2) put_number(o, folders[k].unpack_size);
     any_crc = any_crc || folders[k].crc_defined;
@@ -307,7 +370,8 @@ bool folder_ok(const LzmaGpu7zFolder& f) {
 }
 
 SRes build_header(const LzmaGpu7zFolder* folders, size_t nf, const LzmaGpu7zItem* items, size_t n,
-                  const uint32_t* file_crcs, const UInt16* names, size_t names_len, Bytes& o) {
+                  const uint32_t* file_crcs, const UInt16* names, size_t names_len, Bytes& o,
+                  const LzmaGpu7zBcj2Info* bcj2 = nullptr, size_t n_bcj2 = 0) {
   std::vector<DataFile> files;
   size_t n_empty = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -321,9 +385,16 @@ SRes build_header(const LzmaGpu7zFolder* folders, size_t nf, const LzmaGpu7zItem
       ++n_empty;
   }
   // the folders' files are the data items in order, their sizes the unpack size
-  size_t at = 0;
+  size_t at = 0, n_four = 0;
   for (size_t k = 0; k < nf; ++k) {
-    if (!folder_ok(folders[k]) || folders[k].num_files > files.size() - at) return SZ_ERROR_PARAM;
+    if (folders[k].num_coders == 4) {  // only with its entry, and LZMA as the main coder
+      if (n_four >= n_bcj2 || folders[k].method != kLzma || folders[k].props_size != 5)
+        return SZ_ERROR_PARAM;
+      ++n_four;
+    } else if (!folder_ok(folders[k])) {
+      return SZ_ERROR_PARAM;
+    }
+    if (folders[k].num_files > files.size() - at) return SZ_ERROR_PARAM;
     uint64_t sum = 0;
     for (uint32_t j = 0; j < folders[k].num_files; ++j) sum += files[at + j].size;
     if (sum != folders[k].unpack_size) return SZ_ERROR_PARAM;
@@ -332,7 +403,7 @@ SRes build_header(const LzmaGpu7zFolder* folders, size_t nf, const LzmaGpu7zItem
   if (at != files.size()) return SZ_ERROR_PARAM;
   o.push_back(kHeader);
   o.push_back(kMainStreamsInfo);
-  put_streams_info(o, folders, nf, 0, &files);
+  put_streams_info(o, folders, nf, 0, &files, bcj2);
   o.push_back(kFilesInfo);
   put_number(o, n);
   if (n_empty) {
@@ -496,12 +567,82 @@ bool filtered_ranges_overlap(const Plan& p) {
   uint64_t end_any = 0, end_filtered = 0;
   for (size_t k = 0; k < by.size(); ++k) {
     const FolderPlan& f = p.folders[by[k]];
-    const bool filt = p.methods[f.method].filter != 0;
+    const uint32_t filter = p.methods[f.method].filter;
+    const bool filt = filter != 0 && filter != kFilterBcj2;  // BCJ2 splits out of place
     if (f.off < end_filtered || (filt && f.off < end_any)) return true;
     end_any = std::max(end_any, f.off + f.size);
     if (filt) end_filtered = std::max(end_filtered, f.off + f.size);
   }
   return false;
+}
+
+// A BCJ2 folder's four streams (main, call, jump, rc as Bcj2GpuEncDesc has them)
+// behind the uploaded source, in the same allocation
+struct Bcj2Split {
+  size_t folder;
+  uint64_t off[4], len[4];
+};
+uint64_t lay_out_bcj2(const Plan& p, uint64_t at, std::vector<Bcj2Split>& v) {
+  for (size_t k = 0; k < p.folders.size(); ++k) {
+    if (p.methods[p.folders[k].method].filter != kFilterBcj2) continue;
+    Bcj2Split b;
+    uint64_t cap[4];
+    Bcj2EncGpu_Bound(p.folders[k].size, cap);
+    b.folder = k;
+    for (int j = 0; j < 4; ++j) {
+      b.off[j] = at;
+      b.len[j] = cap[j];  // the capacity until the split has run
+      at += cap[j];
+    }
+    v.push_back(b);
+  }
+  return at;
+}
+// the split of every BCJ2 folder, in launches cut by `limit`; waits and leaves
+// the true lengths in v
+SRes split_bcj2(const Plan& p, std::vector<Bcj2Split>& v, uint8_t* d_src, uint64_t limit) {
+  if (v.empty()) return SZ_OK;
+  std::vector<Bcj2GpuEncDesc> d(v.size());
+  for (size_t i = 0; i < v.size(); ++i) {
+    d[i].src_off = p.folders[v[i].folder].off;
+    d[i].src_len = p.folders[v[i].folder].size;
+    for (int j = 0; j < 4; ++j) {
+      d[i].out[j].off = v[i].off[j];
+      d[i].out[j].cap = v[i].len[j];
+    }
+  }
+  LaunchPlan lp;
+  if (!launch_plan(d.size(), [&](uint32_t i) { return d[i].src_len; },
+                   [&](uint32_t i) { return bcj2enc::slice_bytes(d[i].src_len); },
+                   limit > bcj2enc::fixed_bytes() ? limit - bcj2enc::fixed_bytes() : 0, lp)) {
+    set_error("7z write: one BCJ2 folder's scratch exceeds the limit");
+    return SZ_ERROR_MEM;
+  }
+  const std::vector<Bcj2GpuEncDesc> ordered = in_plan_order(d.data(), lp);
+  DevArr<Bcj2GpuEncDesc> g_d;
+  DevArr<Bcj2GpuEncResult> g_r;
+  DevArr<uint8_t> g_ws;
+  SRes r = upload(g_d, ordered, "7z write");
+  if (r == SZ_OK)
+    r = alloc_all("7z write", g_r, d.size(), g_ws, size_t(lp.ws_max + bcj2enc::fixed_bytes()));
+  if (r == SZ_OK)
+    r = queue_launches("7z write: BCJ2 split", lp, [&](uint32_t lo, uint32_t cnt) {
+      return bcj2encgpu_launch(g_d.p + lo, cnt, d_src, d_src, g_ws.p, g_r.p + lo, kBcj2EncAll,
+                               nullptr);
+    });
+  if (r != SZ_OK) return r;
+  std::vector<Bcj2GpuEncResult> res(d.size());
+  if (!hip_ok(hipDeviceSynchronize(), "7z write: BCJ2 split") ||
+      !download(res, g_r.p, "download BCJ2 lengths"))
+    return SZ_ERROR_FAIL;
+  for (size_t k = 0; k < res.size(); ++k) {
+    if (res[k].res != SZ_OK) {  // the capacities are the bounds
+      set_error("7z write: a BCJ2 split failed on the device");
+      return SZ_ERROR_FAIL;
+    }
+    for (int j = 0; j < 4; ++j) v[lp.order[k]].len[j] = res[k].len[j];
+  }
+  return SZ_OK;
 }
 
 // the header as one more LZMA stream: the batch path with one stream
@@ -567,8 +708,30 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   uint64_t limit = options ? options->workspace_limit : 0;
   if (!default_workspace_limit(limit)) return SZ_ERROR_FAIL;
 
-  // pieces and first-round slots, in folder order
+  // upload, CRCs, filters and the BCJ2 split: queued on the null stream, in order
+  Device g;
+  std::vector<Bcj2Split> bcj2;
+  const uint64_t src_alloc = lay_out_bcj2(p, src_size, bcj2);
+  SRes r;
+  if ((r = alloc_all("7z write", g.src, size_t(src_alloc))) != SZ_OK) return r;
+  if (src_size && !hip_ok(hipMemcpy(g.src.p, src, src_size, hipMemcpyHostToDevice), "upload src"))
+    return SZ_ERROR_FAIL;
+  mark(LZMA_GPU_7Z_STAGE_UPLOAD);
+  RangeChecks crc;
+  FilterJob filt_x86, filt_arm;
+  if ((r = queue_crcs(items, n, g.src.p, crc)) != SZ_OK) return r;
+  mark(LZMA_GPU_7Z_STAGE_CRC);
+  if ((r = queue_filters(p, g.src.p, filt_x86, filt_arm)) != SZ_OK ||
+      (r = split_bcj2(p, bcj2, g.src.p, limit)) != SZ_OK)
+    return r;
+  mark(LZMA_GPU_7Z_STAGE_FILTER);
+
+  // pieces and first-round slots, in folder order; a BCJ2 folder has four pack
+  // streams, each a "folder" of the pack stage
   const size_t nf = p.folders.size();
+  std::vector<uint32_t> pack_first(nf);
+  uint32_t n_pack = 0;
+  size_t next_bcj2 = 0;
   std::vector<SzGpuPackPiece> pieces;
   pieces.reserve(size_t(p.n_pieces));
   std::vector<uint64_t> piece_cap;  // what each piece can add to the pack area
@@ -581,8 +744,43 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
     const Method& m = p.methods[f.method];
     SzGpuPackPiece pc;
     memset(&pc, 0, sizeof(pc));
-    pc.folder = uint32_t(k);
-    if (m.id == kCopy) {
+    pack_first[k] = n_pack;
+    pc.folder = n_pack++;
+    if (m.filter == kFilterBcj2) {
+      const Bcj2Split& b = bcj2[next_bcj2++];
+      n_pack += 3;
+      // main, rc, call, jump: the split's streams main, rc, call, jump
+      static const int kStream[4] = {LZMA_GPU_BCJ2_MAIN, LZMA_GPU_BCJ2_RC, LZMA_GPU_BCJ2_CALL,
+                                     LZMA_GPU_BCJ2_JUMP};
+      for (int j = 0; j < 4; ++j) {
+        const int sidx = kStream[j];
+        pc.folder = pack_first[k] + uint32_t(j);
+        if (sidx == LZMA_GPU_BCJ2_RC) {
+          pc.kind = LZMA_GPU_7Z_PACK_COPY;
+          pc.base = 0;
+          pc.off = b.off[sidx];
+          pc.len = b.len[sidx];
+          pc.slot = 0;
+          pieces.push_back(pc);
+          piece_cap.push_back(pc.len);
+          continue;
+        }
+        LzmaEncGpuStreamDesc d = sidx == LZMA_GPU_BCJ2_MAIN ? m.proto : m.target_proto;
+        d.src_off = b.off[sidx];
+        d.src_len = b.len[sidx];
+        d.dst_off = at;
+        d.dst_cap = first_slot(d.src_len);
+        at += d.dst_cap;
+        pc.kind = LZMA_GPU_7Z_PACK_LZMA;
+        pc.base = 1;
+        pc.off = d.dst_off;
+        pc.len = 0;
+        lz.d.push_back(d);
+        lz.piece.push_back(uint32_t(pieces.size()));
+        pieces.push_back(pc);
+        piece_cap.push_back(d.dst_cap);
+      }
+    } else if (m.id == kCopy) {
       pc.kind = LZMA_GPU_7Z_PACK_COPY;
       pc.base = 0;
       pc.off = f.off;
@@ -640,7 +838,6 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
       piece_cap.push_back(d.dst_cap);
     }
   }
-  SRes r;
   if ((r = lay_out(lz, limit, lzmaenc_slice_bytes)) != SZ_OK || (r = lay_out(l2, limit, lzma2enc_slice_bytes)) != SZ_OK ||
       (r = lay_out(pp, limit, ppmd_slice)) != SZ_OK)
     return r;
@@ -648,23 +845,12 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   for (size_t k = 0; k < l2.d.size(); ++k) pieces[l2.piece[k]].slot = uint32_t(k);
   for (size_t k = 0; k < pp.d.size(); ++k) pieces[pp.piece[k]].slot = uint32_t(k);
 
-  Device g;
   g.ws_bytes = std::max(lz.plan.ws_max, std::max(l2.plan.ws_max, pp.plan.ws_max));
   const size_t lz_cap = lz.d.size() * (1 + kReencodeRounds);
   const size_t pp_cap = pp.d.size() * (1 + kReencodeRounds);
-  if ((r = alloc_all("7z write", g.src, src_size, g.slots, size_t(at), g.ws, size_t(g.ws_bytes),
-                     g.lz_res, lz_cap, g.l2_res, l2.d.size(), g.pp_res, pp_cap)) != SZ_OK)
+  if ((r = alloc_all("7z write", g.slots, size_t(at), g.ws, size_t(g.ws_bytes), g.lz_res, lz_cap,
+                     g.l2_res, l2.d.size(), g.pp_res, pp_cap)) != SZ_OK)
     return r;
-  if (src_size && !hip_ok(hipMemcpy(g.src.p, src, src_size, hipMemcpyHostToDevice), "upload src"))
-    return SZ_ERROR_FAIL;
-  mark(LZMA_GPU_7Z_STAGE_UPLOAD);
-  // everything below is queued on the null stream, in order
-  RangeChecks crc;
-  FilterJob filt_x86, filt_arm;
-  if ((r = queue_crcs(items, n, g.src.p, crc)) != SZ_OK) return r;
-  mark(LZMA_GPU_7Z_STAGE_CRC);
-  if ((r = queue_filters(p, g.src.p, filt_x86, filt_arm)) != SZ_OK) return r;
-  mark(LZMA_GPU_7Z_STAGE_FILTER);
   DevArr<LzmaEncGpuStreamDesc> g_lz, g_l2;
   DevArr<Ppmd7GpuEncDesc> g_pp;
   if ((r = launch_lzma(lz, g_lz, g.src.p, g.slots.p, g.ws.p, g.lz_res.p, &st.encode_launches)) !=
@@ -768,13 +954,13 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   DevArr<LzmaEncGpuResult> g_total;
   if ((r = upload(g_pieces, pieces, "7z write")) != SZ_OK ||
       (r = alloc_all("7z write", g.out, size_t(out_cap), g_scratch, SzGpu_PackScratch(np), g_off,
-                     np, g_fsize, nf, g_total, 1)) != SZ_OK)
+                     np, g_fsize, n_pack, g_total, 1)) != SZ_OK)
     return r;
   SzGpuPackArgs a;
   memset(&a, 0, sizeof(a));
   a.d_pieces = g_pieces.p;
   a.n = np;
-  a.n_folders = nf;
+  a.n_folders = n_pack;
   a.bases[0] = g.src.p;
   a.bases[1] = g.slots.p;
   for (unsigned k = 0; k < kReencodeRounds; ++k) a.bases[2 + k] = g.retry[k].p;
@@ -795,7 +981,7 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
     return SZ_ERROR_FAIL;
   }
   LzmaEncGpuResult total;
-  std::vector<uint64_t> fsize(nf);
+  std::vector<uint64_t> fsize(n_pack);
   std::vector<uint32_t> crcs(crc.n);
   if (!hip_ok(hipDeviceSynchronize(), "7z write: pack") ||
       !hip_ok(hipMemcpy(&total, g_total.p, sizeof(total), hipMemcpyDeviceToHost),
@@ -806,7 +992,7 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
     set_error("7z write: a piece failed on the device");
     return SZ_ERROR_FAIL;
   }
-  if ((nf && !hip_ok(hipMemcpy(fsize.data(), g_fsize.p, nf * 8, hipMemcpyDeviceToHost),
+  if ((n_pack && !hip_ok(hipMemcpy(fsize.data(), g_fsize.p, n_pack * 8, hipMemcpyDeviceToHost),
                      "download pack sizes")) ||
       !crc.fetch(crcs.data(), "download CRCs"))
     return SZ_ERROR_FAIL;
@@ -815,14 +1001,27 @@ SRes write_archive(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,
   std::vector<LzmaGpu7zFolder> folders(nf);
   for (size_t k = 0; k < nf; ++k) {
     fill_folder(p, k, folders[k]);
-    folders[k].pack_size = fsize[k];
+    folders[k].pack_size = fsize[pack_first[k]];
+  }
+  std::vector<LzmaGpu7zBcj2Info> infos(bcj2.size());
+  for (size_t i = 0; i < bcj2.size(); ++i) {
+    const Bcj2Split& b = bcj2[i];
+    const Method& m = p.methods[p.folders[b.folder].method];
+    LzmaGpu7zBcj2Info& o = infos[i];
+    memset(&o, 0, sizeof(o));
+    for (int j = 0; j < 4; ++j) o.pack_size[j] = fsize[pack_first[b.folder] + j];
+    o.unpack_size[0] = b.len[LZMA_GPU_BCJ2_JUMP];
+    o.unpack_size[1] = b.len[LZMA_GPU_BCJ2_CALL];
+    o.unpack_size[2] = b.len[LZMA_GPU_BCJ2_MAIN];
+    memcpy(o.call_props, m.target_props, 5);
+    memcpy(o.jump_props, m.target_props, 5);
   }
   std::vector<uint32_t> file_crcs(n, 0);
   for (size_t i = 0, d = 0; i < n; ++i)
     if (has_data(items[i])) file_crcs[i] = crcs[d++];
   Bytes hdr, hpack;
-  if ((r = build_header(folders.data(), nf, items, n, file_crcs.data(), names, names_len, hdr)) !=
-      SZ_OK)
+  if ((r = build_header(folders.data(), nf, items, n, file_crcs.data(), names, names_len, hdr,
+                        infos.data(), infos.size())) != SZ_OK)
     return r;
   const uint64_t pack_total = total.dest_len;
   if (flags & LZMA_GPU_7Z_WRITE_ENCODE_HEADER) {
@@ -880,11 +1079,34 @@ extern "C" SRes LzmaGpu_7zWritePlan(const LzmaGpu7zItem* items, size_t n, size_t
     if (n_folders) *n_folders = p.folders.size();
     if (n_pieces) *n_pieces = size_t(p.n_pieces);
     if (dest_bound) {
-      const uint64_t hb = header_bound(p.folders.size(), n, names_len);
+      const uint64_t hb = header_bound(p.folders.size(), size_t(p.n_bcj2), n, names_len);
       *dest_bound = 32 + p.pack_bound + lzma_retry_slot(hb, kReencodeRounds) + hb + 64;
     }
     for (size_t k = 0; folders && k < p.folders.size() && k < folder_cap; ++k)
       fill_folder(p, k, folders[k]);
+    return SZ_OK;
+  });
+}
+
+extern "C" SRes LzmaGpu_7zWriteHeaderEx(const LzmaGpu7zFolder* folders, size_t n_folders,
+                                        const LzmaGpu7zItem* items, size_t n,
+                                        const uint32_t* file_crcs, const UInt16* names,
+                                        size_t names_len, unsigned flags,
+                                        const LzmaGpu7zBcj2Info* bcj2, size_t n_bcj2, Byte* header,
+                                        size_t header_cap, size_t* header_len, Byte* sig32,
+                                        uint64_t pack_area_size) {
+  return guarded("7z write: host allocation failed", [&]() -> SRes {
+    if (flags & ~unsigned(LZMA_GPU_7Z_HEADER_STUB)) return SZ_ERROR_PARAM;
+    Bytes o;
+    const SRes r = (flags & LZMA_GPU_7Z_HEADER_STUB)
+                       ? build_stub(folders, n_folders, o)
+                       : build_header(folders, n_folders, items, n, file_crcs, names, names_len, o,
+                                      bcj2, n_bcj2);
+    if (r != SZ_OK) return r;
+    if (header_len) *header_len = o.size();
+    if (sig32) write_sig(sig32, o, pack_area_size);
+    if (!header || header_cap < o.size()) return SZ_ERROR_OUTPUT_EOF;
+    memcpy(header, o.data(), o.size());
     return SZ_OK;
   });
 }
@@ -895,19 +1117,9 @@ extern "C" SRes LzmaGpu_7zWriteHeader(const LzmaGpu7zFolder* folders, size_t n_f
                                       size_t names_len, unsigned flags, Byte* header,
                                       size_t header_cap, size_t* header_len, Byte* sig32,
                                       uint64_t pack_area_size) {
-  return guarded("7z write: host allocation failed", [&]() -> SRes {
-    if (flags & ~unsigned(LZMA_GPU_7Z_HEADER_STUB)) return SZ_ERROR_PARAM;
-    Bytes o;
-    const SRes r = (flags & LZMA_GPU_7Z_HEADER_STUB)
-                       ? build_stub(folders, n_folders, o)
-                       : build_header(folders, n_folders, items, n, file_crcs, names, names_len, o);
-    if (r != SZ_OK) return r;
-    if (header_len) *header_len = o.size();
-    if (sig32) write_sig(sig32, o, pack_area_size);
-    if (!header || header_cap < o.size()) return SZ_ERROR_OUTPUT_EOF;
-    memcpy(header, o.data(), o.size());
-    return SZ_OK;
-  });
+  return LzmaGpu_7zWriteHeaderEx(folders, n_folders, items, n, file_crcs, names, names_len, flags,
+                                 nullptr, 0, header, header_cap, header_len, sig32,
+                                 pack_area_size);
 }
 
 extern "C" SRes LzmaGpu_7zWrite(Byte* dest, SizeT* destLen, const Byte* src, size_t src_size,

@@ -167,6 +167,22 @@ class Bcj2Job(ctypes.Structure):
                 ("out_size", ctypes.c_uint64)]
 
 
+class Bcj2EncRange(ctypes.Structure):
+    """Bcj2GpuEncRange: one output range of a BCJ2 encode, in the destination."""
+    _fields_ = [("off", ctypes.c_uint64), ("cap", ctypes.c_uint64)]
+
+
+class Bcj2EncDesc(ctypes.Structure):
+    """Bcj2GpuEncDesc: one stream of a BCJ2 encode batch; out = main, call, jump, rc."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("src_len", ctypes.c_uint64),
+                ("out", Bcj2EncRange * 4)]
+
+
+class Bcj2EncResult(ctypes.Structure):
+    """Bcj2GpuEncResult: res and the four true lengths (main, call, jump, rc)."""
+    _fields_ = [("res", ctypes.c_int32), ("_pad", ctypes.c_uint32), ("len", ctypes.c_uint64 * 4)]
+
+
 class CSha256(ctypes.Structure):
     """CSha256 (Sha256.h:13-18): the drop-in hash state, the reference's layout."""
     _fields_ = [("state", ctypes.c_uint32 * 8), ("count", ctypes.c_uint64),
@@ -296,6 +312,13 @@ class SzWriteStats(ctypes.Structure):
                 ("stage_ns", ctypes.c_uint64 * 8)]
 
 
+class SzBcj2Info(ctypes.Structure):
+    """LzmaGpu7zBcj2Info: what the header needs for one four-coder (BCJ2) folder."""
+    _fields_ = [("pack_size", ctypes.c_uint64 * 4), ("unpack_size", ctypes.c_uint64 * 3),
+                ("call_props", ctypes.c_ubyte * 5), ("jump_props", ctypes.c_ubyte * 5),
+                ("reserved", ctypes.c_ubyte * 6)]
+
+
 class SzPackPiece(ctypes.Structure):
     """SzGpuPackPiece: one piece of the pack stage's table."""
     _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("slot", ctypes.c_uint32),
@@ -316,6 +339,7 @@ class SzPackArgs(ctypes.Structure):
 
 
 assert ctypes.sizeof(XzBlock) == 104 and ctypes.sizeof(Bcj2Job) == 80
+assert ctypes.sizeof(Bcj2EncDesc) == 80 and ctypes.sizeof(Bcj2EncResult) == 40
 assert ctypes.sizeof(SzFolder) == 80 and ctypes.sizeof(SzFile) == 48
 assert ctypes.sizeof(StreamDesc) == 48 and ctypes.sizeof(Result) == 24
 assert ctypes.sizeof(Session) == 192 and ctypes.sizeof(Plan) == 248
@@ -328,6 +352,7 @@ assert ctypes.sizeof(CLzmaEncProps) == 48
 assert ctypes.sizeof(EncStreamDesc) == 72 and ctypes.sizeof(EncResult) == 16
 assert ctypes.sizeof(SzItem) == 32 and ctypes.sizeof(SzMethod) == 88
 assert ctypes.sizeof(SzWriteOptions) == 16 and ctypes.sizeof(SzWriteStats) == 112
+assert ctypes.sizeof(SzBcj2Info) == 72
 assert ctypes.sizeof(SzPackPiece) == 32 and ctypes.sizeof(SzPackArgs) == 152
 
 _P = ctypes.c_void_p
@@ -388,6 +413,12 @@ _sig = {
     "DeltaGpu_Batch": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_size_t, ctypes.c_int, _P]),
     "Bcj2_Decode": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, ctypes.c_size_t]),
     "Bcj2Gpu_Batch": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P]),
+    "Bcj2EncGpu_Bound": (None, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "Bcj2EncGpu_Scratch": (ctypes.c_uint64, [ctypes.POINTER(Bcj2EncDesc), ctypes.c_size_t]),
+    "Bcj2EncGpu_EncodeBatch": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "Bcj2EncGpu_EncodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Bcj2EncDesc), ctypes.c_size_t, _P,
+                                                  ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                  ctypes.POINTER(Bcj2EncResult), ctypes.c_uint64]),
     "Crc64Calc": (ctypes.c_uint64, [_P, ctypes.c_size_t]),
     "Crc64Gpu_Batch": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P]),
     "Sha256_Init": (None, [ctypes.POINTER(CSha256)]),
@@ -463,6 +494,9 @@ _sig = {
     "LzmaGpu_7zWriteHeader": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P,
                                              ctypes.c_size_t, ctypes.c_uint, _P, ctypes.c_size_t,
                                              _sp, _P, ctypes.c_uint64]),
+    "LzmaGpu_7zWriteHeaderEx": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P,
+                                               ctypes.c_size_t, ctypes.c_uint, _P, ctypes.c_size_t,
+                                               _P, ctypes.c_size_t, _sp, _P, ctypes.c_uint64]),
     "LzmaGpu_7zWrite": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P,
                                        ctypes.c_size_t, _P, ctypes.c_size_t,
                                        ctypes.POINTER(SzWriteOptions),
@@ -887,6 +921,50 @@ def bcj2_batch_device(d_jobs, n, d_res, stream=0):
     return _lib.Bcj2Gpu_Batch(d_jobs, n, d_res, stream or None)
 
 
+def bcj2_bound(n):
+    """Bcj2EncGpu_Bound: capacities for main, call, jump, rc that hold any n bytes."""
+    b = (ctypes.c_uint64 * 4)()
+    _lib.Bcj2EncGpu_Bound(n, b)
+    return list(b)
+
+
+def bcj2_scratch(descs, n):
+    """Bcj2EncGpu_Scratch: the scratch bytes of a batch of n Bcj2EncDesc."""
+    return _lib.Bcj2EncGpu_Scratch(descs, n)
+
+
+def bcj2_encode_batch_device(d_descs, n, d_src, d_dst, d_scratch, d_results, stream=0):
+    """Bcj2EncGpu_EncodeBatch over raw device pointers (ints)."""
+    return _lib.Bcj2EncGpu_EncodeBatch(d_descs, n, d_src, d_dst, d_scratch, d_results,
+                                       stream or None)
+
+
+def bcj2_encode_batch_host(descs, n, src, dst, workspace_limit=0):
+    """Bcj2EncGpu_EncodeBatchHost: dst (bytes) is the output buffer's initial
+    contents.  Returns (res, results[ctypes], dst bytes after the call)."""
+    res = (Bcj2EncResult * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.Bcj2EncGpu_EncodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
+                                        workspace_limit)
+    return r, res, d.raw[:len(dst)]
+
+
+def bcj2_encode(data):
+    """The four BCJ2 streams of x86 code: (main, call, jump, rc), a branch
+    converted when its target lies inside `data`."""
+    cap = bcj2_bound(len(data))
+    desc = (Bcj2EncDesc * 1)()
+    desc[0].src_len = len(data)
+    at = 0
+    for k in range(4):
+        desc[0].out[k].off, desc[0].out[k].cap = at, cap[k]
+        at += cap[k]
+    r, res, out = bcj2_encode_batch_host(desc, 1, data, bytes(at))
+    if r != 0 or res[0].res != 0:
+        raise RuntimeError("bcj2_encode: res %d / %d: %s" % (r, res[0].res, last_error()))
+    return tuple(out[desc[0].out[k].off:desc[0].out[k].off + res[0].len[k]] for k in range(4))
+
+
 def Crc64Calc(data):
     """XzCrc64.c Crc64Calc on the GPU."""
     return _lib.Crc64Calc(_buf(data), len(data))
@@ -1002,7 +1080,7 @@ SZ_WRITE_ENCODE_HEADER, SZ_WRITE_TIMINGS = 1, 2
 SZ_STAGES = ("upload", "crc", "filter", "encode", "pack", "download", "header", "total")
 SZ_HEADER_STUB = 1
 SZ_M_COPY, SZ_M_LZMA, SZ_M_LZMA2, SZ_M_PPMD = 0, 0x030101, 0x21, 0x030401
-SZ_FILTER_X86, SZ_FILTER_ARM = 4, 7
+SZ_FILTER_X86, SZ_FILTER_ARM, SZ_FILTER_BCJ2 = 4, 7, 0x1B
 SZ_PACK_COPY, SZ_PACK_LZMA, SZ_PACK_LZMA2, SZ_PACK_PPMD = 0, 1, 2, 3
 SZ_PACK_LAST = 1
 
@@ -1068,6 +1146,24 @@ def sz_write_header(folders, items, n, file_crcs, names, names_len, flags=0, pac
     out = ctypes.create_string_buffer(max(hl.value, 1))
     r = _lib.LzmaGpu_7zWriteHeader(farr, len(folders), items, n, crcs, names, names_len, flags,
                                    out, hl.value, ctypes.byref(hl), sig, pack_area_size)
+    return r, out.raw[:hl.value], sig.raw
+
+
+def sz_write_header_ex(folders, items, n, file_crcs, names, names_len, bcj2, flags=0,
+                       pack_area_size=0):
+    """LzmaGpu_7zWriteHeaderEx: bcj2 = one SzBcj2Info per four-coder folder, in
+    order.  (res, header bytes, the 32-byte signature header)."""
+    farr = _array(SzFolder, folders)
+    barr = _array(SzBcj2Info, bcj2)
+    crcs = (ctypes.c_uint32 * max(n, 1))(*file_crcs) if file_crcs is not None else None
+    hl = ctypes.c_size_t(0)
+    sig = ctypes.create_string_buffer(32)
+    args = (farr, len(folders), items, n, crcs, names, names_len, flags, barr, len(bcj2))
+    r = _lib.LzmaGpu_7zWriteHeaderEx(*args, None, 0, ctypes.byref(hl), None, 0)
+    if r != SZ_ERROR_OUTPUT_EOF:
+        return r, b"", b""
+    out = ctypes.create_string_buffer(max(hl.value, 1))
+    r = _lib.LzmaGpu_7zWriteHeaderEx(*args, out, hl.value, ctypes.byref(hl), sig, pack_area_size)
     return r, out.raw[:hl.value], sig.raw
 
 
