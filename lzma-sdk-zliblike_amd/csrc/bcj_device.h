@@ -18,7 +18,7 @@
 
 #include <stdint.h>
 
-#include "crc32_device.h"  // u32x4, load16, host-emulation macros
+#include "device_shim.h"  // u32x4, load16
 
 namespace lzgpu {
 

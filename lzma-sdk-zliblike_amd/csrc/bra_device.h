@@ -22,7 +22,7 @@
 
 #include <stdint.h>
 
-#include "crc32_device.h"  // host-emulation macros
+#include "device_shim.h"
 
 namespace lzgpu {
 

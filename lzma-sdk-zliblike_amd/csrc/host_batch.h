@@ -30,6 +30,21 @@ SRes guarded(const char* what, F f) {
   }
 }
 
+// The body of a device-pointer entry point that is one launch over n items
+// (launch() returns 0 on success): no device is SZ_ERROR_FAIL, a count the
+// kernels' 32-bit indices cannot hold is SZ_ERROR_PARAM, a failed launch is
+// "<what> kernel launch failed" and SZ_ERROR_FAIL.
+template <class Launch>
+SRes batch_launch(const char* what, size_t n, Launch launch) {
+  if (!ensure_device()) return SZ_ERROR_FAIL;
+  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
+  if (launch() != 0) {
+    set_error((std::string(what) + " kernel launch failed").c_str());
+    return SZ_ERROR_FAIL;
+  }
+  return SZ_OK;
+}
+
 // ---------------------------------------------------------------- arrays and copies
 
 inline bool alloc_each() { return true; }
@@ -262,32 +277,52 @@ struct RangeChecks {
 // ---------------------------------------------------------------- filters over ranges
 
 struct FilterJob {
+  size_t n = 0;
   DevArr<uint64_t> r64;   // off | len | done
   DevArr<uint32_t> r32;   // ip or distance | x86 state
-  DevArr<uint8_t> state;  // delta
+  DevArr<uint8_t> state;  // delta, 256 bytes per range
+
+  // once the caller has waited: the bytes each range's converter processed
+  // (x86 and the BRA family), the x86 states, the first `bytes` delta state bytes
+  bool fetch_done(uint64_t* done, const char* what) {
+    return hip_ok(hipMemcpy(done, r64.p + 2 * n, 8 * n, hipMemcpyDeviceToHost), what);
+  }
+  bool fetch_x86_state(uint32_t* st, const char* what) {
+    return hip_ok(hipMemcpy(st, r32.p + n, 4 * n, hipMemcpyDeviceToHost), what);
+  }
+  bool fetch_delta_state(uint8_t* st, size_t bytes, const char* what) {
+    return hip_ok(hipMemcpy(st, state.p, bytes, hipMemcpyDeviceToHost), what);
+  }
 };
 
 // One in-place filter (xz filter ids: 3 delta, 4 x86, 5..9 the BRA family) over
 // the ranges [off[i], off[i] + len[i]) of d_data, queued on the null stream;
-// prop[i] is range i's start ip or delta distance (null: 0), states start at 0
-// (x86_Convert_Init, Delta_Init).  j holds the ranges until the caller waits.
+// prop[i] is range i's start ip or delta distance (null: 0).  The states start
+// from x86_state[i] or delta_state[256 i ..], null: 0 (x86_Convert_Init,
+// Delta_Init).  j holds the ranges until the caller waits.
 inline SRes queue_filter(const char* what, FilterJob& j, uint32_t kind, Byte* d_data,
                          const std::vector<uint64_t>& off, const std::vector<uint64_t>& len,
-                         const uint32_t* prop, int encoding) {
-  const size_t n = off.size();
+                         const uint32_t* prop, int encoding, const uint32_t* x86_state = nullptr,
+                         const uint8_t* delta_state = nullptr) {
+  const size_t n = j.n = off.size();
   if (n == 0) return SZ_OK;
   std::vector<uint64_t> h64(off);
   h64.insert(h64.end(), len.begin(), len.end());
   h64.resize(3 * n, 0);
   std::vector<uint32_t> h32(kind == 4 ? 2 * n : n, 0);
   if (prop) std::copy(prop, prop + n, h32.begin());
+  if (kind == 4 && x86_state) std::copy(x86_state, x86_state + n, h32.begin() + n);
   SRes r = upload(j.r64, h64, what);
   if (r == SZ_OK) r = upload(j.r32, h32, what);
   if (r != SZ_OK) return r;
   const uint64_t *d_off = j.r64.p, *d_len = j.r64.p + n;
   if (kind == 3) {
     if ((r = alloc_all(what, j.state, 256 * n)) != SZ_OK) return r;
-    if (!hip_ok(hipMemset(j.state.p, 0, 256 * n), what)) return SZ_ERROR_FAIL;
+    if (!hip_ok(delta_state
+                    ? hipMemcpy(j.state.p, delta_state, 256 * n, hipMemcpyHostToDevice)
+                    : hipMemset(j.state.p, 0, 256 * n),
+                what))
+      return SZ_ERROR_FAIL;
     return DeltaGpu_Batch(d_data, d_off, d_len, j.r32.p, j.state.p, n, encoding, nullptr);
   }
   if (kind == 4)

@@ -1,6 +1,6 @@
 // lzma_capi.hip -- host side of liblzmagpu.so: the batch extension
 // (include/lzma_gpu.h: planner, batch launches, streaming sessions, LZMA2
-// block splitter), the 7zCrc.h drop-ins and the library's shared host state
+// block splitter) and the library's shared host state
 // (device check, per-device call scratch and class-stream pools).  The
 // LzmaDec / LzmaLib / Lzma2Dec drop-ins are in dropin_capi.hip.
 //
@@ -19,7 +19,6 @@
 #include <string>
 #include <vector>
 
-#include "crc32_device.h"
 #include "host_batch.h"
 #include "lzma_device.h"
 #include "lzma_gpu_internal.h"
@@ -299,15 +298,11 @@ SRes LzmaGpu_DecodeBatch(const LzmaGpuStreamDesc* d_descs, const uint32_t* d_ord
                          const Byte* d_src, Byte* d_dst, void* d_workspace, size_t workspace_bytes,
                          LzmaGpuResult* d_results, void* stream) {
   (void)workspace_bytes;
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_decode_batch(d_descs, d_order, uint32_t(n), d_src, d_dst,
-                                static_cast<uint16_t*>(d_workspace), d_results,
-                                static_cast<hipStream_t>(stream)) != 0) {
-    set_error("batch kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
+  return lzgpu_host::batch_launch("batch", n, [&]() {
+    return lzgpu_launch_decode_batch(d_descs, d_order, uint32_t(n), d_src, d_dst,
+                                     static_cast<uint16_t*>(d_workspace), d_results,
+                                     static_cast<hipStream_t>(stream));
+  });
 }
 
 static SRes decode_batch_host(const LzmaGpuStreamDesc* descs, size_t n, const Byte* src,
@@ -448,122 +443,9 @@ SRes LzmaGpu_SessionInit(LzmaGpuSession* s, const Byte* props, unsigned propsSiz
 }
 
 SRes LzmaGpu_SessionDecodeBatch(LzmaGpuSession* d_sessions, size_t n, void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_session(d_sessions, uint32_t(n), static_cast<hipStream_t>(stream)) != 0) {
-    set_error("session kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-// ------------------------------------------------------------------ CRC-32
-
-size_t CrcGpu_PlanChunks(const uint64_t* caps, size_t n, uint32_t* chunk_base,
-                         uint32_t* chunk_range) {
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t c = (caps[i] + lzgpu::kCrcChunk - 1) / lzgpu::kCrcChunk;
-    if (total + c > 0xFFFFFFFFull) return size_t(-1);
-    if (chunk_base) chunk_base[i] = uint32_t(total);
-    if (chunk_range)
-      for (uint64_t k = 0; k < c; ++k) chunk_range[total + k] = uint32_t(i);
-    total += c;
-  }
-  return size_t(total);
-}
-
-size_t LzmaGpu_Crc32Plan(const LzmaGpuStreamDesc* descs, size_t n, uint32_t* chunk_base,
-                         uint32_t* chunk_range) {
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t c = (descs[i].dst_cap + lzgpu::kCrcChunk - 1) / lzgpu::kCrcChunk;
-    if (total + c > 0xFFFFFFFFull) return size_t(-1);
-    if (chunk_base) chunk_base[i] = uint32_t(total);
-    if (chunk_range)
-      for (uint64_t k = 0; k < c; ++k) chunk_range[total + k] = uint32_t(i);
-    total += c;
-  }
-  return size_t(total);
-}
-
-SRes CrcGpu_Batch(const Byte* d_data, const uint64_t* d_off, const uint64_t* d_len, size_t n,
-                  const uint32_t* d_chunk_base, const uint32_t* d_chunk_range, size_t n_chunks,
-                  uint32_t init, uint32_t xorout, uint32_t* d_chunk_crc, uint32_t* d_crc,
-                  void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull || n_chunks > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_crc_arrays(d_data, d_off, d_len, uint32_t(n), d_chunk_base, d_chunk_range,
-                              uint32_t(n_chunks), init, xorout, d_chunk_crc, d_crc,
-                              static_cast<hipStream_t>(stream)) != 0) {
-    set_error("CRC kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-SRes LzmaGpu_Crc32Batch(const LzmaGpuStreamDesc* d_descs, const LzmaGpuResult* d_results,
-                        size_t n, const Byte* d_dst, const uint32_t* d_chunk_base,
-                        const uint32_t* d_chunk_range, size_t n_chunks, uint32_t* d_chunk_crc,
-                        uint32_t* d_crc, void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull || n_chunks > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_crc_decoded(d_descs, d_results, d_dst, uint32_t(n), d_chunk_base,
-                               d_chunk_range, uint32_t(n_chunks), d_chunk_crc, d_crc,
-                               static_cast<hipStream_t>(stream)) != 0) {
-    set_error("CRC kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-// 7zCrc.h drop-ins over host buffers (upload + the batch kernels, n = 1).
-// They cannot report errors; without a device they print once and return 0.
-void CrcGenerateTable(void) {}  // tables are compile-time constants on the device
-
-static uint32_t crc_host_one(uint32_t init, const void* data, size_t size, uint32_t xorout) {
-  if (!ensure_device()) return 0;
-  if (size == 0) return init ^ xorout;
-  lzgpu_host::CallScratch* S = lzgpu_host::scratch_acquire();
-  if (!S) return 0;
-  const uint64_t cap = size;
-  const size_t nch = CrcGpu_PlanChunks(&cap, 1, nullptr, nullptr);
-  // one upload: [offset, length | chunk base | chunk ranges]
-  std::vector<uint32_t> meta(4 + 1 + nch, 0);
-  meta[2] = uint32_t(cap);
-  meta[3] = uint32_t(cap >> 32);
-  CrcGpu_PlanChunks(&cap, 1, meta.data() + 4, meta.data() + 5);
-  uint8_t* d_data = static_cast<uint8_t*>(S->buf[0].get(size));
-  uint8_t* d_meta = static_cast<uint8_t*>(S->buf[1].get(4 * meta.size() + 8));
-  uint32_t* d_chunks = static_cast<uint32_t*>(S->buf[2].get(4 * (nch + 1)));
-  uint32_t out = 0;
-  const hipStream_t st = S->stream;
-  if (!d_data || !d_meta || !d_chunks) {
-    set_error("CRC: device allocation failed");
-  } else {
-    uint64_t* d_ol = reinterpret_cast<uint64_t*>(d_meta);
-    uint32_t* d_base = reinterpret_cast<uint32_t*>(d_meta + 16);
-    uint32_t* d_crc = reinterpret_cast<uint32_t*>(d_meta + 4 * meta.size());
-    if (hip_ok(hipMemcpyAsync(d_data, data, size, hipMemcpyHostToDevice, st), "CRC H2D") &&
-        hip_ok(hipMemcpyAsync(d_meta, meta.data(), 4 * meta.size(), hipMemcpyHostToDevice, st),
-               "CRC H2D") &&
-        lzgpu_launch_crc_arrays(d_data, d_ol, d_ol + 1, 1, d_base, d_base + 1, uint32_t(nch), init,
-                                xorout, d_chunks, d_crc, st) == 0 &&
-        hip_ok(hipMemcpyAsync(&out, d_crc, 4, hipMemcpyDeviceToHost, st), "CRC D2H") &&
-        hip_ok(hipStreamSynchronize(st), "CRC kernel")) {
-    } else {
-      out = 0;
-    }
-  }
-  (void)hipStreamSynchronize(st);  // host buffers are reused after return
-  lzgpu_host::scratch_release(S);
-  return out;
-}
-
-UInt32 CrcUpdate(UInt32 v, const void* data, size_t size) { return crc_host_one(v, data, size, 0); }
-
-UInt32 CrcCalc(const void* data, size_t size) {
-  return crc_host_one(0xFFFFFFFFu, data, size, 0xFFFFFFFFu);
+  return lzgpu_host::batch_launch("session", n, [&]() {
+    return lzgpu_launch_session(d_sessions, uint32_t(n), static_cast<hipStream_t>(stream));
+  });
 }
 
 int LzmaGpu_DeviceCount(void) { return device_count(); }

@@ -33,17 +33,9 @@
 
 #include <type_traits>
 
-#ifdef LZGPU_HOST_EMU
-// Test-only host build of the per-lane logic (tests/emu): lets the CPU test
-// suite exercise exactly this code before it runs on the GPU.  Never part
-// of liblzmagpu.so.
-#include <stddef.h>
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#else
-#include <hip/hip_runtime.h>
-#endif
+// LZGPU_HOST_EMU: the test-only host build of the per-lane logic (tests/emu)
+// lets the CPU test suite exercise exactly this code before it runs on the GPU
+#include "device_shim.h"
 
 namespace lzgpu {
 

@@ -50,29 +50,26 @@ extern "C" int lzgpu_session_launch_shape(uint32_t n, uint32_t lds_cells, uint32
                                           lzgpu_host::LaunchShape* out);
 // rows[4 i ..] = (family, w, mask, k2) of kernel table row i < cap; returns the row count
 extern "C" uint32_t lzgpu_decode_kernel_rows(uint32_t* rows, uint32_t cap);
+// ---- the range primitives (range_capi.hip), 0 on success.  CRC-32 / CRC-64
+// (crc_kernels.hip) over arrays of ranges or a decode batch's own results
 extern "C" int lzgpu_launch_crc_arrays(const uint8_t* d_data, const uint64_t* d_off,
                                        const uint64_t* d_len, uint32_t n,
                                        const uint32_t* d_chunk_base,
                                        const uint32_t* d_chunk_range, uint32_t n_chunks,
                                        uint32_t init, uint32_t xorout, uint32_t* d_chunk_crc,
                                        uint32_t* d_crc, hipStream_t stream);
+extern "C" int lzgpu_launch_crc_decoded(const LzmaGpuStreamDesc* d_descs,
+                                        const LzmaGpuResult* d_results, const uint8_t* d_dst,
+                                        uint32_t n, const uint32_t* d_chunk_base,
+                                        const uint32_t* d_chunk_range, uint32_t n_chunks,
+                                        uint32_t* d_chunk_crc, uint32_t* d_crc,
+                                        hipStream_t stream);
 extern "C" int lzgpu_launch_crc64_arrays(const uint8_t* d_data, const uint64_t* d_off,
                                          const uint64_t* d_len, uint32_t n,
                                          const uint32_t* d_chunk_base,
                                          const uint32_t* d_chunk_range, uint32_t n_chunks,
                                          uint64_t init, uint64_t xorout, uint64_t* d_chunk_crc,
                                          uint64_t* d_crc, hipStream_t stream);
-extern "C" int lzgpu_launch_bcj_x86(uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
-                                    const uint32_t* d_ip, uint32_t* d_state, uint64_t* d_done,
-                                    uint32_t n, int encoding, hipStream_t stream);
-extern "C" int lzgpu_launch_bra(uint32_t kind, uint8_t* d_data, const uint64_t* d_off,
-                                const uint64_t* d_len, const uint32_t* d_ip, uint64_t* d_done,
-                                uint32_t n, int encoding, hipStream_t stream);
-extern "C" int lzgpu_launch_bcj2(const Bcj2GpuJob* d_jobs, uint32_t n, int32_t* d_res,
-                                 hipStream_t stream);
-extern "C" int lzgpu_launch_delta(uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
-                                  const uint32_t* d_delta, uint8_t* d_state, uint32_t n,
-                                  int encoding, hipStream_t stream);
 // SHA-256 of n device ranges d_data[off[i] .. off[i] + len[i]) (sha256_kernels.hip),
 // the one launcher behind Sha256Gpu_Batch, the Sha256.h drop-ins and the xz
 // block check.  Range i continues from the chaining state d_init[8 * i .. + 8)
@@ -97,8 +94,20 @@ extern "C" int lzgpu_launch_sha256(const uint8_t* d_data, const uint64_t* d_off,
                                    const uint64_t* d_len, uint32_t n, const uint32_t* d_init,
                                    const uint64_t* d_prior, int finalise, unsigned kernel,
                                    uint8_t* d_out, hipStream_t stream);
+// the filters (filter_kernels.hip)
+extern "C" int lzgpu_launch_bcj_x86(uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
+                                    const uint32_t* d_ip, uint32_t* d_state, uint64_t* d_done,
+                                    uint32_t n, int encoding, hipStream_t stream);
+extern "C" int lzgpu_launch_bra(uint32_t kind, uint8_t* d_data, const uint64_t* d_off,
+                                const uint64_t* d_len, const uint32_t* d_ip, uint64_t* d_done,
+                                uint32_t n, int encoding, hipStream_t stream);
+extern "C" int lzgpu_launch_bcj2(const Bcj2GpuJob* d_jobs, uint32_t n, int32_t* d_res,
+                                 hipStream_t stream);
+extern "C" int lzgpu_launch_delta(uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
+                                  const uint32_t* d_delta, uint8_t* d_state, uint32_t n,
+                                  int encoding, hipStream_t stream);
 
-// host-side helpers shared by the C-ABI translation units (lzma_capi.hip)
+// host-side helpers shared by the C-ABI translation units (defined in lzma_capi.hip)
 namespace lzgpu_host {
 
 bool ensure_device();
@@ -194,10 +203,3 @@ struct DevArr {
   bool alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)) == hipSuccess; }
 };
 }  // namespace lzgpu_host
-
-extern "C" int lzgpu_launch_crc_decoded(const LzmaGpuStreamDesc* d_descs,
-                                        const LzmaGpuResult* d_results, const uint8_t* d_dst,
-                                        uint32_t n, const uint32_t* d_chunk_base,
-                                        const uint32_t* d_chunk_range, uint32_t n_chunks,
-                                        uint32_t* d_chunk_crc, uint32_t* d_crc,
-                                        hipStream_t stream);

@@ -220,7 +220,7 @@ LZENC_HD void write_props5(const Params& q, uint8_t* props5) {
 }
 
 // p->crc[] of the match finder (LzFind.c:141-148): the project's CRC-32 table
-// (slice 0 of crc32_device.h's CrcTables, polynomial kCrcPoly), entry v
+// (slice 0 of crc_device.h's CrcTables<uint32_t>, polynomial 0xEDB88320), entry v
 LZENC_HD uint32_t crc_entry(uint32_t v) {
   uint32_t r = v;
   for (int j = 0; j < 8; ++j) r = (r >> 1) ^ ((r & 1u) ? 0xEDB88320u : 0u);

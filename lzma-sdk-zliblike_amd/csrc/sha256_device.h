@@ -21,12 +21,7 @@
 
 #include <stdint.h>
 
-#ifdef LZGPU_HOST_EMU
-#ifndef __device__
-#define __device__
-#define __forceinline__ inline
-#endif
-#endif
+#include "device_shim.h"
 
 namespace lzgpu {
 

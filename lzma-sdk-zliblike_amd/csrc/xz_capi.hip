@@ -1,14 +1,13 @@
-// xz_capi.hip -- host side of the xz block batch, x86 BCJ, CRC-64 and SHA-256
-// C ABI
-// (include/lzma_gpu.h).
+// xz_capi.hip -- the xz container: its index (LzmaGpu_XzIndex) and the block
+// batch (LzmaGpu_XzDecode) (include/lzma_gpu.h).
 //
 // The reference reads xz strictly forward (XzUnpacker_Code, XzDec.c:604-870)
 // or indexes it backwards from the footer (Xzs_ReadBackward, XzIn.c:141-306).
 // Here the backward index is the plan: every block of every stream becomes
 // one LZMA2 item of a single GPU batch (LzmaGpu_PlanBatchEx /
-// LzmaGpu_DecodeBatchEx), followed by the x86 BCJ kernel for blocks that
-// carry the filter and the CRC-32 / CRC-64 / SHA-256 kernels for the block
-// checks.
+// LzmaGpu_DecodeBatchEx), followed by the filter kernels for blocks that
+// carry a filter chain and the CRC-32 / CRC-64 / SHA-256 kernels for the block
+// checks (the range primitives, range_capi.hip, through host_batch.h).
 // The host keeps what the reference keeps outside its coders: container
 // parsing with its small CRC-32s (stream header, block headers, index,
 // footer) and the comparison of the computed checks with the stored fields.
@@ -243,377 +242,6 @@ static SRes xz_index(const Byte* file, size_t size, LzmaGpuXzBlock* blocks, size
   if (blocks)
     for (size_t i = 0; i < v.size() && i < cap; ++i) blocks[i] = v[i];
   return SZ_OK;
-}
-
-SRes BcjGpu_X86Batch(Byte* d_data, const uint64_t* d_off, const uint64_t* d_len,
-                     const uint32_t* d_ip, uint32_t* d_state, uint64_t* d_done, size_t n,
-                     int encoding, void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_bcj_x86(d_data, d_off, d_len, d_ip, d_state, d_done, uint32_t(n), encoding,
-                           static_cast<hipStream_t>(stream)) != 0) {
-    set_error("BCJ kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-SRes Crc64Gpu_Batch(const Byte* d_data, const uint64_t* d_off, const uint64_t* d_len, size_t n,
-                    const uint32_t* d_chunk_base, const uint32_t* d_chunk_range, size_t n_chunks,
-                    uint64_t init, uint64_t xorout, uint64_t* d_chunk_crc, uint64_t* d_crc,
-                    void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull || n_chunks > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_crc64_arrays(d_data, d_off, d_len, uint32_t(n), d_chunk_base, d_chunk_range,
-                                uint32_t(n_chunks), init, xorout, d_chunk_crc, d_crc,
-                                static_cast<hipStream_t>(stream)) != 0) {
-    set_error("CRC-64 kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-// x86_Convert over a host buffer: upload, one lane, download
-SizeT x86_Convert(Byte* data, SizeT size, UInt32 ip, UInt32* state, int encoding) {
-  if (!ensure_device()) return 0;
-  if (size < 5) return 0;
-  DevArr<Byte> d;
-  DevArr<uint64_t> meta;  // off, len, done
-  DevArr<uint32_t> m32;   // ip, state
-  const uint64_t ol[2] = {0, uint64_t(size)};
-  const uint32_t is[2] = {ip, *state};
-  uint64_t done = 0;
-  uint32_t st = 0;
-  if (alloc_all("x86_Convert", d, size, meta, 3, m32, 2) != SZ_OK) return 0;
-  if (!hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), "x86_Convert H2D") ||
-      !hip_ok(hipMemcpy(meta.p, ol, 16, hipMemcpyHostToDevice), "x86_Convert H2D") ||
-      !hip_ok(hipMemcpy(m32.p, is, 8, hipMemcpyHostToDevice), "x86_Convert H2D"))
-    return 0;
-  if (lzgpu_launch_bcj_x86(d.p, meta.p, meta.p + 1, m32.p, m32.p + 1, meta.p + 2, 1, encoding,
-                           nullptr) != 0 ||
-      !hip_ok(hipDeviceSynchronize(), "x86_Convert kernel") ||
-      !hip_ok(hipMemcpy(data, d.p, size, hipMemcpyDeviceToHost), "x86_Convert D2H") ||
-      !hip_ok(hipMemcpy(&done, meta.p + 2, 8, hipMemcpyDeviceToHost), "x86_Convert D2H") ||
-      !hip_ok(hipMemcpy(&st, m32.p + 1, 4, hipMemcpyDeviceToHost), "x86_Convert D2H"))
-    return 0;
-  *state = st;
-  return SizeT(done);
-}
-
-namespace {
-
-bool bra_kind_ok(unsigned kind) {
-  return kind == 5 || kind == 6 || kind == 7 || kind == 8 || kind == 9;
-}
-
-// one RISC converter over a host buffer: upload, one range, download
-SizeT bra_convert_host(unsigned kind, const char* name, Byte* data, SizeT size, UInt32 ip,
-                       int encoding) {
-  if (!ensure_device()) return 0;
-  if (size < (kind == 6 ? 16u : 4u)) return 0;
-  DevArr<Byte> d;
-  DevArr<uint64_t> meta;  // off, len, done
-  DevArr<uint32_t> m32;   // ip
-  const uint64_t ol[2] = {0, uint64_t(size)};
-  uint64_t done = 0;
-  if (alloc_all("Bra converter", d, size, meta, 3, m32, 1) != SZ_OK) return 0;
-  if (!hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), name) ||
-      !hip_ok(hipMemcpy(meta.p, ol, 16, hipMemcpyHostToDevice), name) ||
-      !hip_ok(hipMemcpy(m32.p, &ip, 4, hipMemcpyHostToDevice), name))
-    return 0;
-  if (lzgpu_launch_bra(kind, d.p, meta.p, meta.p + 1, m32.p, meta.p + 2, 1, encoding, nullptr) !=
-          0 ||
-      !hip_ok(hipDeviceSynchronize(), name) ||
-      !hip_ok(hipMemcpy(data, d.p, size, hipMemcpyDeviceToHost), name) ||
-      !hip_ok(hipMemcpy(&done, meta.p + 2, 8, hipMemcpyDeviceToHost), name))
-    return 0;
-  return SizeT(done);
-}
-
-void delta_host(Byte* state, unsigned delta, Byte* data, SizeT size, int encoding) {
-  if (!ensure_device()) return;
-  if (delta == 0 || delta > 256) {
-    set_error("Delta: delta outside 1..256");
-    return;
-  }
-  DevArr<Byte> d, st;
-  DevArr<uint64_t> meta;  // off, len
-  DevArr<uint32_t> dl;
-  const uint64_t ol[2] = {0, uint64_t(size)};
-  if (alloc_all("Delta", d, size, st, 256, meta, 2, dl, 1) != SZ_OK) return;
-  if ((size && !hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), "Delta H2D")) ||
-      !hip_ok(hipMemcpy(st.p, state, delta, hipMemcpyHostToDevice), "Delta H2D") ||
-      !hip_ok(hipMemcpy(meta.p, ol, 16, hipMemcpyHostToDevice), "Delta H2D") ||
-      !hip_ok(hipMemcpy(dl.p, &delta, 4, hipMemcpyHostToDevice), "Delta H2D"))
-    return;
-  if (lzgpu_launch_delta(d.p, meta.p, meta.p + 1, dl.p, st.p, 1, encoding, nullptr) != 0 ||
-      !hip_ok(hipDeviceSynchronize(), "Delta kernel") ||
-      (size && !hip_ok(hipMemcpy(data, d.p, size, hipMemcpyDeviceToHost), "Delta D2H")) ||
-      !hip_ok(hipMemcpy(state, st.p, delta, hipMemcpyDeviceToHost), "Delta D2H"))
-    return;
-}
-
-}  // namespace
-
-SizeT ARM_Convert(Byte* data, SizeT size, UInt32 ip, int encoding) {
-  return bra_convert_host(7, "ARM_Convert", data, size, ip, encoding);
-}
-SizeT ARMT_Convert(Byte* data, SizeT size, UInt32 ip, int encoding) {
-  return bra_convert_host(8, "ARMT_Convert", data, size, ip, encoding);
-}
-SizeT PPC_Convert(Byte* data, SizeT size, UInt32 ip, int encoding) {
-  return bra_convert_host(5, "PPC_Convert", data, size, ip, encoding);
-}
-SizeT SPARC_Convert(Byte* data, SizeT size, UInt32 ip, int encoding) {
-  return bra_convert_host(9, "SPARC_Convert", data, size, ip, encoding);
-}
-SizeT IA64_Convert(Byte* data, SizeT size, UInt32 ip, int encoding) {
-  return bra_convert_host(6, "IA64_Convert", data, size, ip, encoding);
-}
-void Delta_Init(Byte* state) { memset(state, 0, 256); }
-void Delta_Encode(Byte* state, unsigned delta, Byte* data, SizeT size) {
-  delta_host(state, delta, data, size, 1);
-}
-void Delta_Decode(Byte* state, unsigned delta, Byte* data, SizeT size) {
-  delta_host(state, delta, data, size, 0);
-}
-
-SRes BraGpu_Batch(unsigned kind, Byte* d_data, const uint64_t* d_off, const uint64_t* d_len,
-                  const uint32_t* d_ip, uint64_t* d_done, size_t n, int encoding, void* stream) {
-  if (!bra_kind_ok(kind)) return SZ_ERROR_UNSUPPORTED;
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_bra(kind, d_data, d_off, d_len, d_ip, d_done, uint32_t(n), encoding,
-                       static_cast<hipStream_t>(stream)) != 0) {
-    set_error("branch converter kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-SRes DeltaGpu_Batch(Byte* d_data, const uint64_t* d_off, const uint64_t* d_len,
-                    const uint32_t* d_delta, Byte* d_state, size_t n, int encoding, void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_delta(d_data, d_off, d_len, d_delta, d_state, uint32_t(n), encoding,
-                         static_cast<hipStream_t>(stream)) != 0) {
-    set_error("delta kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-SRes Bcj2Gpu_Batch(const Bcj2GpuJob* d_jobs, size_t n, int32_t* d_res, void* stream) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (lzgpu_launch_bcj2(d_jobs, uint32_t(n), d_res, static_cast<hipStream_t>(stream)) != 0) {
-    set_error("BCJ2 kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-// Bcj2_Decode over host buffers: the four streams and the output go to the
-// device (buf0 inside outBuf, as 7zDec.c:367-372 places it, stays inside the
-// device copy of outBuf at the same offset), one lane decodes, the output
-// comes back.
-static int bcj2_host(const Byte* buf0, SizeT size0, const Byte* buf1, SizeT size1,
-                     const Byte* buf2, SizeT size2, const Byte* buf3, SizeT size3, Byte* outBuf,
-                     SizeT outSize) {
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  const uintptr_t o0 = uintptr_t(outBuf), o1 = o0 + outSize, b0 = uintptr_t(buf0);
-  const bool inside = size0 && b0 >= o0 && b0 < o1;
-  // device layout: [out (+ main tail beyond it) | buf0 | buf1 | buf2 | buf3]
-  const uint64_t out_room = inside ? std::max<uint64_t>(outSize, (b0 - o0) + size0) : outSize;
-  const uint64_t off0 = out_room, off1 = off0 + (inside ? 0 : size0), off2 = off1 + size1,
-                 off3 = off2 + size2, total = off3 + size3;
-  DevArr<Byte> d;
-  DevArr<Bcj2GpuJob> dj;
-  DevArr<int32_t> dr;
-  const SRes ar = alloc_all("Bcj2_Decode", d, size_t(total), dj, 1, dr, 1);
-  if (ar != SZ_OK) return ar;
-  auto up = [&](uint64_t at, const Byte* p, uint64_t n) {
-    return n == 0 || hip_ok(hipMemcpy(d.p + at, p, size_t(n), hipMemcpyHostToDevice), "Bcj2 H2D");
-  };
-  bool ok = true;
-  if (inside) {
-    // the host bytes of outBuf (main stream included) and any main tail beyond it
-    ok = up(0, outBuf, outSize);
-    if (ok && (b0 - o0) + size0 > outSize)
-      ok = up(outSize, reinterpret_cast<const Byte*>(o1), (b0 - o0) + size0 - outSize);
-  } else {
-    // bytes the decoder does not write (an error exit) keep the caller's values
-    ok = up(0, outBuf, outSize) && up(off0, buf0, size0);
-  }
-  ok = ok && up(off1, buf1, size1) && up(off2, buf2, size2) && up(off3, buf3, size3);
-  if (!ok) return SZ_ERROR_FAIL;
-  Bcj2GpuJob j;
-  j.buf0 = inside ? d.p + (b0 - o0) : d.p + off0;
-  j.buf1 = d.p + off1;
-  j.buf2 = d.p + off2;
-  j.buf3 = d.p + off3;
-  j.size0 = size0;
-  j.size1 = size1;
-  j.size2 = size2;
-  j.size3 = size3;
-  j.out = d.p;
-  j.out_size = outSize;
-  int32_t r = SZ_ERROR_FAIL;
-  if (!hip_ok(hipMemcpy(dj.p, &j, sizeof j, hipMemcpyHostToDevice), "Bcj2 H2D") ||
-      Bcj2Gpu_Batch(dj.p, 1, dr.p, nullptr) != SZ_OK || !hip_ok(hipDeviceSynchronize(), "Bcj2") ||
-      !hip_ok(hipMemcpy(&r, dr.p, 4, hipMemcpyDeviceToHost), "Bcj2 D2H") ||
-      (outSize && !hip_ok(hipMemcpy(outBuf, d.p, outSize, hipMemcpyDeviceToHost), "Bcj2 D2H")))
-    return SZ_ERROR_FAIL;
-  return r;
-}
-
-int Bcj2_Decode(const Byte* buf0, SizeT size0, const Byte* buf1, SizeT size1, const Byte* buf2,
-                SizeT size2, const Byte* buf3, SizeT size3, Byte* outBuf, SizeT outSize) {
-  return guarded("Bcj2_Decode: host allocation failed", [&]() {
-    return bcj2_host(buf0, size0, buf1, size1, buf2, size2, buf3, size3, outBuf, outSize);
-  });
-}
-
-UInt64 Crc64Calc(const void* data, size_t size) {
-  if (!ensure_device()) return 0;
-  if (size == 0) return 0;
-  const uint64_t cap = size;
-  const size_t nch = CrcGpu_PlanChunks(&cap, 1, nullptr, nullptr);
-  std::vector<uint32_t> meta(1 + nch);
-  CrcGpu_PlanChunks(&cap, 1, meta.data(), meta.data() + 1);
-  DevArr<Byte> d;
-  DevArr<uint64_t> ol, chunks;
-  DevArr<uint32_t> m;
-  const uint64_t olh[3] = {0, cap, 0};
-  if (alloc_all("Crc64Calc", d, size, ol, 3, chunks, nch, m, 1 + nch) != SZ_OK) return 0;
-  uint64_t out = 0;
-  if (!hip_ok(hipMemcpy(d.p, data, size, hipMemcpyHostToDevice), "CRC-64 H2D") ||
-      !hip_ok(hipMemcpy(ol.p, olh, 24, hipMemcpyHostToDevice), "CRC-64 H2D") ||
-      !hip_ok(hipMemcpy(m.p, meta.data(), 4 * (1 + nch), hipMemcpyHostToDevice), "CRC-64 H2D"))
-    return 0;
-  if (lzgpu_launch_crc64_arrays(d.p, ol.p, ol.p + 1, 1, m.p, m.p + 1, uint32_t(nch), ~0ull, ~0ull,
-                                chunks.p, ol.p + 2, nullptr) != 0 ||
-      !hip_ok(hipDeviceSynchronize(), "CRC-64 kernel") ||
-      !hip_ok(hipMemcpy(&out, ol.p + 2, 8, hipMemcpyDeviceToHost), "CRC-64 D2H"))
-    return 0;
-  return out;
-}
-
-// ---- SHA-256 C ABI: the Sha256.h drop-ins over host buffers and the batch
-// form over device ranges.  No compression function lives on the host: it
-// buffers bytes until a block is complete, as Sha256_Update does
-// (Sha256.c:160-174), and every block, the padding blocks included, is
-// compressed by lzgpu_launch_sha256 (sha256_kernels.hip).
-static_assert(sizeof(CSha256) == 104, "CSha256 layout (Sha256.h:13-18)");
-
-// The kernels' translation unit is part of the library.  A host-only link of
-// the container parsers that leaves it out (the sanitizer build of
-// tests/fuzz/) still links: the reference is weak, and a call without the
-// kernels is an error, never a host computation.
-extern "C" __attribute__((weak)) int lzgpu_launch_sha256(
-    const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len, uint32_t n,
-    const uint32_t* d_init, const uint64_t* d_prior, int finalise, unsigned kernel,
-    uint8_t* d_out, hipStream_t stream);
-
-static int sha256_launch(const uint8_t* d_data, const uint64_t* d_off, const uint64_t* d_len,
-                         uint32_t n, const uint32_t* d_init, const uint64_t* d_prior,
-                         int finalise, unsigned kernel, uint8_t* d_out, hipStream_t stream) {
-  if (!lzgpu_launch_sha256) return -3;
-  return lzgpu_launch_sha256(d_data, d_off, d_len, n, d_init, d_prior, finalise, kernel, d_out,
-                             stream);
-}
-
-SRes Sha256Gpu_Batch(const Byte* d_data, const uint64_t* d_off, const uint64_t* d_len, size_t n,
-                     unsigned kernel, Byte* d_digest, void* stream) {
-  if (kernel > LZMA_GPU_SHA256_WAVE || n > 0xFFFFFFFFull) return SZ_ERROR_PARAM;
-  if (!ensure_device()) return SZ_ERROR_FAIL;
-  if (sha256_launch(d_data, d_off, d_len, uint32_t(n), nullptr, nullptr, 1, kernel,
-                          d_digest, static_cast<hipStream_t>(stream)) != 0) {
-    set_error("SHA-256 kernel launch failed");
-    return SZ_ERROR_FAIL;
-  }
-  return SZ_OK;
-}
-
-namespace {
-
-// One range on the device: head (the bytes buffered in the struct) followed by
-// body, continued from `state` with `prior` bytes hashed before.  finalise:
-// out = the 32 digest bytes; else out = the state after the whole blocks.
-// One message is one serial chain: the wave kernel.
-bool sha256_host_range(const uint32_t state[8], uint64_t prior, const Byte* head, size_t n_head,
-                       const Byte* body, size_t n_body, int finalise, void* out) {
-  lzgpu_host::CallScratch* S = lzgpu_host::scratch_acquire();
-  if (!S) return false;
-  const size_t size = n_head + n_body;
-  // one upload: [offset, length, prior | state | 32 bytes of result]
-  uint64_t meta[3 + 4] = {0, uint64_t(size), prior};
-  memcpy(meta + 3, state, 32);
-  uint8_t* d_data = static_cast<uint8_t*>(S->buf[0].get(size));
-  uint8_t* d_meta = static_cast<uint8_t*>(S->buf[1].get(sizeof meta + 32));
-  const hipStream_t st = S->stream;
-  bool ok = false;
-  if (!d_data || !d_meta) {
-    set_error("SHA-256: device allocation failed");
-  } else {
-    uint64_t* d_m = reinterpret_cast<uint64_t*>(d_meta);
-    ok = (n_head == 0 ||
-          hip_ok(hipMemcpyAsync(d_data, head, n_head, hipMemcpyHostToDevice, st), "SHA-256 H2D")) &&
-         (n_body == 0 || hip_ok(hipMemcpyAsync(d_data + n_head, body, n_body,
-                                               hipMemcpyHostToDevice, st),
-                                "SHA-256 H2D")) &&
-         hip_ok(hipMemcpyAsync(d_meta, meta, sizeof meta, hipMemcpyHostToDevice, st),
-                "SHA-256 H2D");
-    if (ok && sha256_launch(d_data, d_m, d_m + 1, 1, reinterpret_cast<uint32_t*>(d_m + 3),
-                                  d_m + 2, finalise, kLzgpuSha256Wave, d_meta + sizeof meta,
-                                  st) != 0) {
-      set_error("SHA-256 kernel launch failed");
-      ok = false;
-    }
-    ok = ok &&
-         hip_ok(hipMemcpyAsync(out, d_meta + sizeof meta, 32, hipMemcpyDeviceToHost, st),
-                "SHA-256 D2H") &&
-         hip_ok(hipStreamSynchronize(st), "SHA-256 kernel");
-  }
-  (void)hipStreamSynchronize(st);  // host buffers are reused after return
-  lzgpu_host::scratch_release(S);
-  return ok;
-}
-
-}  // namespace
-
-void Sha256_Init(CSha256* p) {
-  static const UInt32 iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                               0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-  memcpy(p->state, iv, sizeof iv);
-  p->count = 0;
-}
-
-void Sha256_Update(CSha256* p, const Byte* data, size_t size) {
-  const size_t fill = size_t(p->count & 0x3F);
-  if (size < 64 - fill) {  // no block completes: buffer only
-    if (size) memcpy(p->buffer + fill, data, size);
-    p->count += size;
-    return;
-  }
-  // the buffered bytes and the data up to the last block boundary go to the
-  // device; what is left over becomes the new buffer contents
-  const size_t whole = ((fill + size) & ~size_t(63)) - fill, rest = size - whole;
-  if (ensure_device()) {
-    UInt32 st[8];
-    if (sha256_host_range(p->state, p->count - fill, p->buffer, fill, data, whole, 0, st))
-      memcpy(p->state, st, sizeof st);
-  }
-  if (rest) memcpy(p->buffer, data + whole, rest);
-  p->count += size;
-}
-
-void Sha256_Final(CSha256* p, Byte* digest) {
-  const size_t fill = size_t(p->count & 0x3F);
-  if (!ensure_device() ||
-      !sha256_host_range(p->state, p->count - fill, p->buffer, fill, nullptr, 0, 1, digest))
-    memset(digest, 0, SHA256_DIGEST_SIZE);
-  Sha256_Init(p);
 }
 
 static SRes xz_decode(Byte* dest, SizeT* destLen, const Byte* file, size_t size,

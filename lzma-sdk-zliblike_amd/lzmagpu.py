@@ -810,7 +810,7 @@ def split_lzma2_blocks(src):
 
 # ---------------------------------------------------------------- CRC-32 (7zCrc.h)
 
-CRC_CHUNK = 2048  # kCrcChunk in csrc/crc32_device.h
+CRC_CHUNK = 2048  # kCrcChunk in csrc/crc_device.h (CRC-32 and CRC-64)
 
 
 def CrcCalc(data):

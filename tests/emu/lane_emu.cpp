@@ -10,13 +10,28 @@
 #include <vector>
 
 #include "../../lzma-sdk-zliblike_amd/csrc/lzma_lane.h"
-#include "../../lzma-sdk-zliblike_amd/csrc/crc32_device.h"
-#include "../../lzma-sdk-zliblike_amd/csrc/crc64_device.h"
+#include "../../lzma-sdk-zliblike_amd/csrc/crc_device.h"
 #include "../../lzma-sdk-zliblike_amd/csrc/bcj_device.h"
 #include "../../lzma-sdk-zliblike_amd/csrc/bcj2_device.h"
 #include "../../lzma-sdk-zliblike_amd/csrc/bra_device.h"
 
 using namespace lzgpu;
+
+// The CRC kernels' per-lane code (crc_chunk per chunk slot, then crc_fold),
+// range by range.  The blocks read may extend up to 15 bytes either side of a
+// range (aligned 16-byte loads): callers pad their buffers.
+template <class R>
+static void crc_ranges(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
+                       R init, R xorout, R* out) {
+  static const CrcTables<R> T = crc_make_tables<R>();
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t nch = (len[i] + kCrcChunk - 1) / kCrcChunk;
+    std::vector<R> c(nch + 1);
+    for (uint64_t j = 0; j < nch; ++j)
+      crc_chunk<R>(&T.slice[0][0], data + off[i], len[i], uint32_t(j), init, &c[j]);
+    out[i] = crc_fold<R>(&T.shift[0][0], c.data(), len[i], init) ^ xorout;
+  }
+}
 
 extern "C" {
 
@@ -184,32 +199,15 @@ int emu_stream_decode_dic(const uint8_t* props, const uint8_t* src, size_t src_t
                        trace, max_calls, out_len, in_used, 0);
 }
 
-// CRC-32 kernels' per-lane code (crc_chunk per chunk slot, then crc_fold),
-// range by range.  The blocks read may extend up to 15 bytes either side of a
-// range (aligned 16-byte loads): callers pad their buffers.
+// CRC-32 and CRC-64 through crc_ranges
 void emu_crc_ranges(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
                     uint32_t init, uint32_t xorout, uint32_t* out) {
-  static const CrcTables T = crc_make_tables();
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t nch = (len[i] + kCrcChunk - 1) / kCrcChunk;
-    std::vector<uint32_t> c(nch + 1);
-    for (uint64_t j = 0; j < nch; ++j)
-      crc_chunk(&T.slice[0][0], data + off[i], len[i], uint32_t(j), init, &c[j]);
-    out[i] = crc_fold(&T.shift[0][0], c.data(), len[i], init) ^ xorout;
-  }
+  crc_ranges(data, off, len, n, init, xorout, out);
 }
 
-// CRC-64 kernels' per-lane code (crc64_chunk per chunk slot, then crc64_fold).
 void emu_crc64_ranges(const uint8_t* data, const uint64_t* off, const uint64_t* len, size_t n,
                       uint64_t init, uint64_t xorout, uint64_t* out) {
-  static const Crc64Tables T = crc64_make_tables();
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t nch = (len[i] + kCrc64Chunk - 1) / kCrc64Chunk;
-    std::vector<uint64_t> c(nch + 1);
-    for (uint64_t j = 0; j < nch; ++j)
-      crc64_chunk(&T.slice[0][0], data + off[i], len[i], uint32_t(j), init, &c[j]);
-    out[i] = crc64_fold(&T.shift[0][0], c.data(), len[i], init) ^ xorout;
-  }
+  crc_ranges(data, off, len, n, init, xorout, out);
 }
 
 // The x86 BCJ kernel's per-lane code (bcj_x86) on one buffer.  The window

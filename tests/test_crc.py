@@ -109,6 +109,20 @@ def test_chunk_plan():
         for k in range(w):
             assert rng[acc + k] == i
         acc += w
+    # LzmaGpu_Crc32Plan is the same plan over the descriptors' dst_cap
+    descs = L.make_descs([dict(src_off=0, src_len=0, dst_off=0, dst_cap=c, props=b"")
+                          for c in caps])
+    dbase, drng, dtotal = L.crc32_plan_decoded(descs)
+    assert dtotal == total
+    assert list(dbase)[:len(caps)] == list(base)[:len(caps)]
+    assert list(drng)[:total] == list(rng)[:total]
+    # more chunk slots than a 32-bit index holds: (size_t)-1 from both
+    none = ctypes.c_size_t(-1).value
+    big = [1 << 43, 1 << 43]
+    assert L.lib.CrcGpu_PlanChunks((ctypes.c_uint64 * 2)(*big), 2, None, None) == none
+    bdescs = L.make_descs([dict(src_off=0, src_len=0, dst_off=0, dst_cap=c, props=b"")
+                           for c in big])
+    assert L.lib.LzmaGpu_Crc32Plan(bdescs, 2, None, None) == none
 
 
 # ---------------------------------------------------------------- GPU

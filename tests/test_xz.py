@@ -9,7 +9,8 @@ CPU (no GPU): the index (LzmaGpu_XzIndex is host code) against the
 reference's decoded sizes and error codes; the BCJ and CRC-64 kernels'
 per-lane code (host build, tests/emu) against the reference's outputs.
 GPU (-m gpu): LzmaGpu_XzDecode on every fixture file, the x86_Convert and
-Crc64Calc drop-ins, and a many-block file decoded as one batch.
+Crc64Calc drop-ins, Crc64Gpu_Batch over all CRC-64 fixtures in one call, and a
+many-block file decoded as one batch.
 """
 import ctypes
 import hashlib
@@ -173,6 +174,72 @@ def test_crc64_emu_matches_reference(emu):
         out = (ctypes.c_uint64 * 1)()
         emu.emu_crc64_ranges(buf, off, ln, 1, 2**64 - 1, 2**64 - 1, out)
         assert out[0] == c["crc64"], c
+
+
+def crc64_layout(d, phase):
+    """The crc64 fixture slices in one buffer, slice i starting at phase
+    (phase + i) mod 16 of a 16-byte block, 48-byte margins: (buf, offs, lens)."""
+    buf, offs, lens = bytearray(b"\xAA" * 48), [], []
+    for i, c in enumerate(d["crc64"]):
+        buf += b"\x55" * ((phase + i - len(buf)) % 16)
+        offs.append(len(buf))
+        lens.append(c["len"])
+        buf += d["blob"][c["off"]:c["off"] + c["len"]]
+    return bytes(buf + b"\xAA" * 48), offs, lens
+
+
+def test_crc64_emu_every_phase(emu):
+    """All fixture slices (the lengths at which the head block, the short chunk
+    0 and the fold can go wrong) as one call of n ranges, at every start phase
+    of a 16-byte block."""
+    d = fixtures()
+    want = [c["crc64"] for c in d["crc64"]]
+    assert [c["len"] for c in d["crc64"]] == [0, 1, 7, 8, 15, 16, 17, 2047, 2048, 2049, 6000,
+                                              100003]
+    n = len(want)
+    for phase in range(16):
+        buf, offs, lens = crc64_layout(d, phase)
+        assert offs[0] % 16 == phase
+        # the copy the emulation reads is 16-byte aligned as the layout assumes
+        cbuf = ctypes.create_string_buffer(len(buf) + 16)
+        shift = -ctypes.addressof(cbuf) % 16
+        ctypes.memmove(ctypes.addressof(cbuf) + shift, buf, len(buf))
+        offs = [o + shift for o in offs]
+        off = (ctypes.c_uint64 * n)(*offs)
+        ln = (ctypes.c_uint64 * n)(*lens)
+        out = (ctypes.c_uint64 * n)()
+        emu.emu_crc64_ranges(cbuf, off, ln, n, 2**64 - 1, 2**64 - 1, out)
+        assert list(out) == want, phase
+
+
+@pytest.mark.gpu
+def test_gpu_crc64_batch_fixtures(L):
+    """Crc64Gpu_Batch over all fixture slices in one device buffer (slice i at
+    phase i mod 16, a zero-length range among them, chunk bases that do not
+    start at 0), then once more with the ranges in reverse order."""
+    import torch
+    d = fixtures()
+    want = [c["crc64"] for c in d["crc64"]]
+    buf, offs, lens = crc64_layout(d, 0)
+    n = len(want)
+    dev = torch.device("cuda")
+    d_data = torch.frombuffer(bytearray(buf), dtype=torch.uint8).to(dev)
+    assert d_data.data_ptr() % 16 == 0
+    for order in (list(range(n)), list(range(n))[::-1]):
+        o, l = [offs[i] for i in order], [lens[i] for i in order]
+        base, crange, total = L.crc_plan(l)
+        d_off = torch.tensor(o, dtype=torch.int64, device=dev)
+        d_len = torch.tensor(l, dtype=torch.int64, device=dev)
+        d_base = torch.tensor(list(base)[:n], dtype=torch.int32, device=dev)
+        d_range = torch.tensor(list(crange)[:total], dtype=torch.int32, device=dev)
+        d_chunks = torch.empty(total, dtype=torch.int64, device=dev)
+        d_crc = torch.empty(n, dtype=torch.int64, device=dev)
+        assert L.crc64_batch_device(d_data.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n,
+                                    d_base.data_ptr(), d_range.data_ptr(), total, 2**64 - 1,
+                                    2**64 - 1, d_chunks.data_ptr(), d_crc.data_ptr()) == 0
+        torch.cuda.synchronize()
+        got = [v & (2**64 - 1) for v in d_crc.cpu().tolist()]
+        assert got == [want[i] for i in order], order
 
 
 @pytest.mark.gpu
