@@ -305,6 +305,10 @@ __device__ __forceinline__ int session_to_dic(LzgpuSession& q, uint64_t dic_limi
 template <uint32_t M = 0u, class Lo = gu16*>
 __device__ __forceinline__ void lane_session(LzgpuSession& q, Lo lo = Lo(), lds_u8* win = nullptr,
                                              uint32_t win_bytes = 0) {
+  // q.probs may be a caller's CLzmaDec table (the drop-in), host-edited cells
+  // included: decision form 1's 16-bit update is exact only on cells the
+  // kernel initialised itself (LZGPU_BIT_FORM, lzma_device.h)
+  static_assert(!bit_form<M>(), "lane_session decodes on caller-owned probabilities: form 0 only");
   int status = kStNone;
   LzWin w = win_make(win, win_bytes, q.dic_buf_size);
   if constexpr (win_on<M>()) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../lzma-sdk-zliblike_amd/csrc/lzma_lane.h"
+#include "../../lzma-sdk-zliblike_amd/csrc/sliced_device.h"
 #include "../../lzma-sdk-zliblike_amd/csrc/crc_device.h"
 #include "../../lzma-sdk-zliblike_amd/csrc/bcj_device.h"
 #include "../../lzma-sdk-zliblike_amd/csrc/bcj2_device.h"
@@ -197,6 +198,63 @@ int emu_stream_decode_dic(const uint8_t* props, const uint8_t* src, size_t src_t
                           size_t* in_used) {
   return stream_decode(props, src, src_total, out, out_total, in_chunk, out_chunk, finish_mode,
                        trace, max_calls, out_len, in_used, 0);
+}
+
+// One call on each of n sessions (host pointers): lzgpu_session_kernel's
+// lanes one after another, or under EMU_SESS_COOP_WIN the cooperative session
+// kernel's workgroups.
+void emu_session_batch(LzgpuSession* sess, size_t n) {
+  for (size_t i = 0; i < n; ++i) run_session(sess[i]);
+}
+
+// The time-sliced batch kernels' stream (sliced.hip): LzmaDecode as rounds of
+// at most `slice` output bytes, each round the kernels' own sliced_step on the
+// spilled session, until the stream is done.  The placement is run_session's:
+// the table in place (lzgpu_sliced_global_kernel), or under EMU_SESS_COOP_WIN
+// the cooperative kernel's -- staged into an "LDS" copy for the round and
+// written back if the stream goes on (sliced_step passes no history window).
+// row: {res, status, dest_len, src_len}.  Returns the rounds run (every round
+// but the last fills its slice, so there are at most cap / slice + 1).
+int emu_sliced_decode(const uint8_t* props, const uint8_t* src, size_t n, uint8_t* dst, size_t cap,
+                      uint64_t slice, int finish, long long* row) {
+  LzmaGpuResult r;
+  r.res = kOk;
+  r.status = -1;
+  r.dest_len = 0;
+  r.src_len = 0;
+  LzgpuSession q;
+  memset(&q, 0, sizeof q);
+  // lzgpu_sliced_init_kernel: the failures LzmaDecode reports before decoding
+  if (n < 5) r.res = kErrInputEof;
+  else r.res = lz_props_parse(props, 5, q.lc, q.lp, q.pb, q.dict_size);
+  int rounds = 0;
+  if (r.res == kOk) {
+    const uint32_t cells = table_cells(q.lc, q.lp, q.pb);
+    std::vector<uint16_t> table(cells + 8, 0xA5A5);  // the workspace is not zeroed
+    q.probs = table.data();
+    q.dic = dst;
+    q.in = src;
+    q.dic_buf_size = cap;
+    q.in_len = n;
+    sliced_reset(q);
+    q.finish_mode = finish;
+    for (bool done = false; !done;) {
+#if defined(EMU_SESS_COOP_WIN)
+      std::vector<uint16_t> lo(cells + 8, 0x5C5C);  // stale LDS contents
+      if (!q.need_init_state) memcpy(lo.data(), q.probs, size_t(cells) * 2);
+      done = sliced_step<LZGPU_LDS_MASK_ALL | kCoopBit>(q, slice, lo.data(), r);
+      if (!done) memcpy((void*)q.probs, lo.data(), size_t(cells) * 2);
+#else
+      done = sliced_step<0u>(q, slice, (gu16*)q.probs, r);
+#endif
+      ++rounds;
+    }
+  }
+  row[0] = r.res;
+  row[1] = r.status;
+  row[2] = (long long)r.dest_len;
+  row[3] = (long long)r.src_len;
+  return rounds;
 }
 
 // CRC-32 and CRC-64 through crc_ranges

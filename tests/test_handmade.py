@@ -5,7 +5,9 @@ recorded results equal the live reference's, and the CPU restatement
 (oracle/liboracle.so) equals the reference on every case.  The host builds of
 the lane code take the set in tests/test_emu.py and tests/test_fuse_emu.py,
 the GPU kernels in tests/test_gpu_kernels.py, tests/test_fuse_gpu.py and
-tests/test_gpu_parity.py."""
+tests/test_gpu_parity.py; the kernels that resume in mid-stream (time-sliced
+rounds, device sessions, the drop-in's DecodeToBuf) in
+tests/test_handmade_resume.py."""
 import collections
 import hashlib
 
