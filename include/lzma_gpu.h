@@ -41,12 +41,17 @@
  *       Lzma2Enc_Encode         replaces Lzma2Enc.h:42-43 / Lzma2Enc.c:434-477
  *                               (differences: at its declaration below)
  *
- *     Encoding covers the reference's fast path only (algo 0 with the hash-chain
- *     finder, what levels 0..4 select): the output is the reference's, bit for
- *     bit.  Documented differences of LzmaEncode / LzmaCompress: props that
- *     normalise to the optimal parser (algo 1) or a bt* finder (btMode 1) --
- *     the default level 5 among them -- return SZ_ERROR_UNSUPPORTED with nothing
- *     written, and LzmaGpu_LastError() says so; a source of 2^31 bytes or more
+ *     Encoding covers the reference's fast path (algo 0 with the hash-chain
+ *     finder, what levels 0..4 select) and, once switched on with
+ *     LzmaEncGpu_SetModes or LZGPU_ENC_MODES, its normal mode (the optimal
+ *     parser and the Bt4 finder, levels 5..9): the output is that of the
+ *     reference's single-threaded encoder, bit for bit.  Documented differences
+ *     of LzmaEncode / LzmaCompress: props that normalise to a mode the mask
+ *     does not allow -- with the initial mask of 0 the optimal parser (algo 1)
+ *     and every bt finder (btMode 1), the default level 5 among them; with any
+ *     mask Bt2 and Bt3 (numHashBytes below 4) -- return SZ_ERROR_UNSUPPORTED
+ *     with nothing written, and LzmaGpu_LastError() names the props field; a
+ *     source of 2^31 bytes or more
  *     returns SZ_ERROR_UNSUPPORTED; `progress` is ignored and the allocators
  *     are unused; LzmaEncProps_Normalize sets numThreads as a build with
  *     threads does, and the value is unused.
@@ -931,19 +936,27 @@ SRes Ppmd7Gpu_EncodeBatchHost(const Ppmd7GpuEncDesc *descs, size_t n, const Byte
                               Byte *dst, size_t dst_size, Ppmd7GpuEncResult *results,
                               uint64_t workspace_limit);
 
-/* ---------------------------------------------------------------- LZMA fast-mode encoding */
+/* ---------------------------------------------------------------- LZMA encoding */
 
-/* The reference's encoder for props that normalise to algo == 0 and
- * btMode == 0 (LzmaEncProps_Normalize, LzmaEnc.c:53-74: levels 0..4): the Hc4
- * hash-chain finder, GetOptimumFast and the range coder, one stream per lane,
- * many independent streams per launch (csrc/lzmaenc_device.h).  Per stream the
+/* The reference's encoder, one stream per lane, many independent streams per
+ * launch (csrc/lzmaenc_device.h).  Mode 0 is what props that normalise to
+ * algo == 0 and btMode == 0 select (LzmaEncProps_Normalize, LzmaEnc.c:53-74:
+ * levels 0..4): the Hc4 hash-chain finder, GetOptimumFast and the range coder.
+ * The normal modes -- the optimal parser (GetOptimum, algo == 1) and / or the
+ * binary-tree finder Bt4 (btMode == 1 with numHashBytes 4), what levels 5..9
+ * select -- run in a kernel of their own and are opt-in (LzmaEncGpu_SetModes
+ * below): they take a larger workspace slice and far longer per byte.  In every
+ * mode the bytes are those of the reference's single-threaded LzmaEncode
+ * (a build with _7ZIP_ST); nothing is claimed about its multi-threaded match
+ * finder, and numThreads is ignored.  Per stream the
  * outcome is LzmaEncode's over a buffer of dst_cap bytes:
  *   SZ_OK                 dest_len bytes written
  *   SZ_ERROR_OUTPUT_EOF   the stream is longer than dst_cap: dest_len == dst_cap
  *                         and dst holds the first dst_cap bytes of the stream
  *   SZ_ERROR_PARAM        lc > 8, lp > 4, pb > 4, dict_size 0 or above 1 << 30,
- *                         fb outside 5..273, or ws_off not a multiple of 16;
- *                         nothing read or written
+ *                         fb outside 5..273, mode above 3, or ws_off not a
+ *                         multiple of 16; nothing read or written, and the
+ *                         stream takes no workspace slice
  *   SZ_ERROR_UNSUPPORTED  src_len >= 2^31; nothing read or written
  * Bytes of d_dst outside [dst_off, dst_off + dest_len) are not written and
  * bytes of d_src outside [src_off, src_off + src_len) are not read. */
@@ -982,8 +995,11 @@ typedef struct LzmaEncGpuStreamDesc {
   uint32_t fb;        /* numFastBytes, 5..273 */
   uint32_t mc;        /* the hash chain's cut value */
   uint32_t write_end_mark;
-  uint32_t reserved;  /* 0 */
+  uint32_t mode;      /* LZMA_ENC_GPU_MODE_* bits; 0 = the fast path */
 } LzmaEncGpuStreamDesc;
+
+#define LZMA_ENC_GPU_MODE_OPTIMAL 1u  /* GetOptimum: algo == 1 */
+#define LZMA_ENC_GPU_MODE_BT4 2u      /* Bt4: btMode == 1, numHashBytes 4 */
 
 /* Per-stream outcome (16 bytes). */
 typedef struct LzmaEncGpuResult {
@@ -1003,20 +1019,47 @@ typedef struct LzmaEncGpuResult {
  * up in the header only).  On an error neither is written. */
 SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps *props, int writeEndMark,
                               LzmaEncGpuStreamDesc *desc, Byte props5[5]);
+/* The modes the calls that take props may select.  A process-wide atomic mask
+ * of LZMA_ENC_GPU_MODE_* bits; its initial value is 0, or the decimal value of
+ * the environment variable LZGPU_ENC_MODES, read once.  With the mask at 0
+ * every call behaves as described for the fast path alone.  It governs
+ * LzmaEncGpu_DescFromProps, Lzma2EncGpu_DescFromProps, LzmaEncode,
+ * LzmaCompress, Lzma2Enc_Encode, LzmaGpu_Lzma2EncodeHost, LzmaGpu_XzEncode and
+ * the LZMA / LZMA2 / BCJ2 folders of LzmaGpu_7zWritePlan and LzmaGpu_7zWrite.
+ * SetModes returns the previous mask (bits above 3 are dropped). */
+unsigned LzmaEncGpu_SetModes(unsigned allowed);
+unsigned LzmaEncGpu_GetModes(void);
+/* LzmaEncGpu_DescFromProps with the mask given by the caller: algo == 1 passes
+ * when `allowed` has LZMA_ENC_GPU_MODE_OPTIMAL, btMode == 1 when it has
+ * LZMA_ENC_GPU_MODE_BT4 and numHashBytes normalises to 4 (Bt2 and Bt3 are
+ * SZ_ERROR_UNSUPPORTED whatever the mask).  desc->mode receives the modes the
+ * props select.  LzmaGpu_LastError() names the props field that was refused. */
+SRes LzmaEncGpu_DescFromPropsEx(const CLzmaEncProps *props, int writeEndMark, unsigned allowed,
+                                LzmaEncGpuStreamDesc *desc, Byte props5[5]);
 /* Host only.  Lays the workspace out: descs[i].ws_off = start of stream i's
  * slice (probability cells, the `matches` array, the hash, the `son` ring sized
- * by min(dict_size, src_len) + 1; a multiple of 256 bytes; a stream the kernel
- * rejects takes none) and *workspace_bytes = their sum.  order (n entries, may
- * be NULL) receives the stream indices longest source first, the order the
- * lanes should take them in.  SZ_ERROR_PARAM for n above 2^31 - 1. */
+ * by min(dict_size, src_len) + 1 -- twice that with Bt4 -- and, with the
+ * optimal parser, the price tables (up to 38 KiB) and the 4,096 `opt` cells
+ * (192 KiB); a multiple of 256 bytes; a stream the kernel rejects takes none)
+ * and *workspace_bytes = their sum.  The hash is sized by dict_size, not by the
+ * source (the reference's hash mask comes from the dictionary, so a smaller one
+ * would change the output): level 5's default dictionary of 16 MiB costs about
+ * 32 MiB per stream however short the stream, so callers with many small
+ * streams should set dictSize.  order (n entries, may be NULL) receives the
+ * stream indices grouped by mode -- optimal parser with Bt4, optimal parser
+ * with Hc4, Bt4 with the fast parser, then mode 0 -- and within a mode longest
+ * source first: the order the lanes should take them in (with every stream at
+ * mode 0, longest source first).  SZ_ERROR_PARAM for n above 2^31 - 1. */
 SRes LzmaEncGpu_PlanBatch(LzmaEncGpuStreamDesc *descs, size_t n, uint32_t *order,
                           uint64_t *workspace_bytes);
 /* Encode n streams on the current device.  All pointers are device memory
  * owned by the caller; d_order (n indices, e.g. LzmaEncGpu_PlanBatch's) may be
  * NULL for index order; the workspace needs no initialisation (the call clears
  * the hashes and sets the probability cells with the whole grid before the
- * encode kernel).  lanes: streams per 64-lane wave, 64, 32, 16 or
- * LZMA_ENC_GPU_LANES_DEFAULT.  Asynchronous on `stream`; n == 0 is a no-op.
+ * encode kernels: one for mode 0 and one for the normal modes, each walking
+ * the same order; a lane whose stream belongs to the other returns at once).
+ * lanes: streams per 64-lane wave, 64, 32, 16 or LZMA_ENC_GPU_LANES_DEFAULT
+ * (the library's choice per kernel).  Asynchronous on `stream`; n == 0 is a no-op.
  * Returns SZ_OK if the launches were queued (SZ_ERROR_FAIL without a device,
  * SZ_ERROR_PARAM for n above 2^31 - 1 or an unknown lanes value); per-stream
  * outcomes land in d_results[i] for stream i. */
@@ -1097,6 +1140,10 @@ size_t Lzma2EncGpu_BlockBound(size_t src_len);
  * LzmaEncGpu_DescFromProps' over the normalised lzmaProps.  On SZ_OK the props
  * fields of *desc are set and *prop is Lzma2Enc_WriteProperties' byte. */
 SRes Lzma2EncGpu_DescFromProps(const CLzma2EncProps *props, LzmaEncGpuStreamDesc *desc, Byte *prop);
+/* The same with the caller's mask of modes in place of LzmaEncGpu_GetModes()
+ * (see LzmaEncGpu_DescFromPropsEx). */
+SRes Lzma2EncGpu_DescFromPropsEx(const CLzma2EncProps *props, unsigned allowed,
+                                 LzmaEncGpuStreamDesc *desc, Byte *prop);
 /* LzmaEncGpu_PlanBatch over the LZMA2 slices (the LZMA slice plus the table
  * that holds the saved probability cells of the chunk in flight). */
 SRes Lzma2EncGpu_PlanBatch(LzmaEncGpuStreamDesc *descs, size_t n, uint32_t *order,
@@ -1252,7 +1299,8 @@ SRes LzmaGpu_7zExtractEx(Byte *dest, SizeT *destLen, const Byte *archive, size_t
  * when its target lies inside the folder's data (a JOIN group: the whole
  * group).  The split (Bcj2EncGpu_EncodeBatch's kernels) is out of place, so a
  * BCJ2 folder's source range may overlap another folder's.
- * Not written: the optimal parser (levels 5+), BCJ2 over LZMA2, PPMd7 or Copy
+ * Levels 5 and up need the modes switched on (LzmaEncGpu_SetModes).
+ * Not written: BCJ2 over LZMA2, PPMd7 or Copy
  * rows, times and attributes, an archive that does not fit in device memory at
  * once. */
 
@@ -1278,7 +1326,8 @@ typedef struct LzmaGpu7zItem {     /* 32 bytes */
  * rows only: SZ_ERROR_UNSUPPORTED on another row; any other value
  * SZ_ERROR_PARAM).  The props go
  * through LzmaEncGpu_DescFromProps / Lzma2EncGpu_DescFromProps: their
- * SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED (level 5 and up) stand. */
+ * SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED (level 5 and up, unless
+ * LzmaEncGpu_SetModes allows them) stand. */
 #define LZMA_GPU_7Z_FILTER_BCJ2 0x1Bu
 typedef struct LzmaGpu7zMethod {   /* 88 bytes */
   uint64_t method;

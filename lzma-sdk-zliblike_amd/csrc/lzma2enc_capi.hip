@@ -42,10 +42,6 @@ extern "C" size_t Lzma2EncGpu_BlockBound(size_t src_len) {
   return src_len + (src_len >> 10) + 16;
 }
 
-static const char kNotFastPath[] =
-    "LZMA encode: props normalise to the optimal parser (algo 1) or a bt match finder "
-    "(btMode 1); only the fast path (levels 0..4: algo 0, btMode 0) is built";
-
 static void fill_desc(LzmaEncGpuStreamDesc* desc, const lzenc::Params& q) {
   desc->dict_size = q.dict_size;
   desc->lc = q.lc;
@@ -54,20 +50,33 @@ static void fill_desc(LzmaEncGpuStreamDesc* desc, const lzenc::Params& q) {
   desc->fb = q.fb;
   desc->mc = q.mc;
   desc->write_end_mark = 0;
-  desc->reserved = 0;
+  desc->mode = lzenc::mode_of(q);
 }
 
-extern "C" SRes Lzma2EncGpu_DescFromProps(const CLzma2EncProps* props, LzmaEncGpuStreamDesc* desc,
-                                          Byte* prop) {
+// lzma2_params_from_props_ex with the refusal put into the last error
+static int32_t params_of(const lzenc::Enc2Props* e, uint32_t allowed, lzenc::Params* q,
+                         uint8_t* prop) {
+  const char* field = nullptr;
+  const int32_t r = lzenc::lzma2_params_from_props_ex(e, allowed, q, prop, &field);
+  if (r == lzenc::kErrUnsupported) lzmaenc_set_unsupported_error(field);
+  return r;
+}
+
+extern "C" SRes Lzma2EncGpu_DescFromPropsEx(const CLzma2EncProps* props, unsigned allowed,
+                                            LzmaEncGpuStreamDesc* desc, Byte* prop) {
   const lzenc::Enc2Props e = to_enc2(props);
   lzenc::Params q;
   uint8_t pr = 0;
-  const int32_t r = lzenc::lzma2_params_from_props(&e, &q, &pr);
-  if (r == lzenc::kErrUnsupported) set_error(kNotFastPath);
+  const int32_t r = params_of(&e, allowed, &q, &pr);
   if (r != lzenc::kOk) return r;
   fill_desc(desc, q);
   *prop = pr;
   return SZ_OK;
+}
+
+extern "C" SRes Lzma2EncGpu_DescFromProps(const CLzma2EncProps* props, LzmaEncGpuStreamDesc* desc,
+                                          Byte* prop) {
+  return Lzma2EncGpu_DescFromPropsEx(props, lzmaenc_allowed_modes(), desc, prop);
 }
 
 extern "C" SRes Lzma2EncGpu_PlanBatch(LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order,
@@ -81,7 +90,7 @@ extern "C" SRes Lzma2EncGpu_PlanBatch(LzmaEncGpuStreamDesc* descs, size_t n, uin
       at += need;
     }
     if (workspace_bytes) *workspace_bytes = at;
-    if (order) longest_first(n, [&](uint32_t i) { return descs[i].src_len; }, order);
+    if (order) longest_first(n, [&](uint32_t i) { return lzmaenc_work(descs[i]); }, order);
     return SZ_OK;
   });
 }
@@ -93,8 +102,8 @@ extern "C" SRes Lzma2EncGpu_EncodeBatch(const LzmaEncGpuStreamDesc* d_descs,
                                         void* stream) {
   if (!ensure_device()) return SZ_ERROR_FAIL;
   if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  if (lanes == LZMA_ENC_GPU_LANES_DEFAULT) lanes = kLzmaEncLanesDefault;
-  if (lanes != 16 && lanes != 32 && lanes != 64) return SZ_ERROR_PARAM;
+  if (lanes != LZMA_ENC_GPU_LANES_DEFAULT && lanes != 16 && lanes != 32 && lanes != 64)
+    return SZ_ERROR_PARAM;
   if (n == 0) return SZ_OK;
   if (lzma2encgpu_launch(d_descs, d_order, 0, uint32_t(n), uint32_t(n), d_src, d_dst,
                          static_cast<uint8_t*>(d_workspace), d_results, lanes,
@@ -134,13 +143,16 @@ SRes run_batch(const LzmaEncGpuStreamDesc* descs, size_t n, const Byte* src, siz
   const SRes r = b.lay_out(
       what, descs, n, src_size, dst_size, workspace_limit,
       [](const LzmaEncGpuStreamDesc& d) { return d.dst_cap; },
-      [](const LzmaEncGpuStreamDesc& d) { return d.src_len; }, lzma2enc_slice_bytes);
+      lzmaenc_work, lzma2enc_slice_bytes);
   if (r != SZ_OK) return r;
-  return b.queue(what, in_caller_order(descs, b.plan), true, src, src_size, dst_init, dst_size,
+  // over the descriptors the device sees: the caller's ws_off is not looked at
+  const std::vector<LzmaEncGpuStreamDesc> d = in_caller_order(descs, b.plan);
+  const uint32_t kernels = lzmaenc_kernels(d.data(), n, lzma2enc_check);
+  return b.queue(what, d, true, src, src_size, dst_init, dst_size,
                  [&](uint32_t lo, uint32_t cnt) {
                    return lzma2encgpu_launch(b.desc.p, b.order.p, lo, cnt, uint32_t(n), b.src.p,
-                                             b.dst.p, b.ws.p, b.res.p, kLzmaEncLanesDefault,
-                                             nullptr);
+                                             b.dst.p, b.ws.p, b.res.p, LZMA_ENC_GPU_LANES_DEFAULT,
+                                             nullptr, kernels);
                  });
 }
 
@@ -150,8 +162,7 @@ SRes resolve_props(const CLzma2EncProps* props, lzenc::Enc2Props* norm, lzenc::P
                    Byte* prop) {
   const lzenc::Enc2Props e = to_enc2(props);
   uint8_t pr = 0;
-  const int32_t r = lzenc::lzma2_params_from_props(&e, q, &pr);
-  if (r == lzenc::kErrUnsupported) set_error(kNotFastPath);
+  const int32_t r = params_of(&e, lzmaenc_allowed_modes(), q, &pr);
   if (r != lzenc::kOk) return r;
   *norm = e;
   lzenc::props2_normalize(norm);
@@ -377,8 +388,7 @@ SRes lzma2enc_encode(Handle* h, ISeqOutStream* outStream, ISeqInStream* inStream
   // Lzma2EncInt_Init's LzmaEnc_SetProps, then what this library does not encode
   lzenc::Params q;
   uint8_t prop;
-  const int32_t pr = lzenc::lzma2_params_from_props(&h->props, &q, &prop);
-  if (pr == lzenc::kErrUnsupported) set_error(kNotFastPath);
+  const int32_t pr = params_of(&h->props, lzmaenc_allowed_modes(), &q, &prop);
   if (pr != lzenc::kOk) return pr;
   if (!ensure_device()) return SZ_ERROR_FAIL;
   std::vector<uint8_t> src;

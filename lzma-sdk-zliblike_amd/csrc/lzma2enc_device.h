@@ -39,8 +39,7 @@
 namespace lzenc {
 
 constexpr int32_t kErrFail = 11;
-constexpr uint32_t kNumOpts = 1u << 12;
-constexpr uint32_t kLzma2PackMax = 1u << 16, kLzma2UnpackMax = 1u << 21;
+constexpr uint32_t kLzma2PackMax = kChunkPackMax, kLzma2UnpackMax = kChunkUnpackMax;
 constexpr uint32_t kLzma2CopyChunk = 1u << 16;
 constexpr uint32_t kLzma2LcLpMax = 4;
 
@@ -119,18 +118,23 @@ LZENC_HD void props2_normalize(Enc2Props* p) {
 // Lzma2Enc_SetProps' check (Lzma2Enc.c:411-421), then Lzma2EncInt_Init's
 // LzmaEnc_SetProps as params_from_props states it.  q and prop are written
 // only on SZ_OK; prop is Lzma2Enc_WriteProperties' byte.
-LZENC_HD int32_t lzma2_params_from_props(const Enc2Props* props, Params* q, uint8_t* prop) {
+// `allowed` and `field` as params_from_props_ex's.
+LZENC_HD int32_t lzma2_params_from_props_ex(const Enc2Props* props, uint32_t allowed, Params* q,
+                                            uint8_t* prop, const char** field = nullptr) {
   EncProps lzmaProps = props->lzmaProps;
   props_normalize(&lzmaProps);
   if (lzmaProps.lc + lzmaProps.lp > int(kLzma2LcLpMax)) return kErrParam;
   Enc2Props n = *props;
   props2_normalize(&n);
   Params t;
-  const int32_t r = params_from_props(&n.lzmaProps, 0, &t);
+  const int32_t r = params_from_props_ex(&n.lzmaProps, 0, allowed, &t, field);
   if (r != kOk) return r;
   *q = t;
   *prop = lzma2_prop_byte(t.dict_size);
   return kOk;
+}
+LZENC_HD int32_t lzma2_params_from_props(const Enc2Props* props, Params* q, uint8_t* prop) {
+  return lzma2_params_from_props_ex(props, 0, q, prop);
 }
 
 // One block's slice: the LZMA slice, then the saved probability table
@@ -161,110 +165,178 @@ LZENC_FN void copy16(uint8_t* to, const uint8_t* from, uint64_t n) {
   }
 }
 
-struct Lzma2Enc : LzmaEnc {
-  // LzmaEnc_CodeOneBlock(p, True, 1 << 16, 1 << 21): LzmaEnc::code_one_block
-  // with the chunk limits in place of the 32 KiB progress step, always ending
-  // in Flush.  The token coding in the middle is the same text.
+// kNormal as LzmaEncT's: false is the fast path alone, true the reference's
+// encoder with its two mode bits at run time.
+template <bool kNormal>
+struct Lzma2EncT : LzmaEncT<kNormal> {
+  using B = LzmaEncT<kNormal>;
+  using B::additionalOffset;
+  using B::cache;
+  using B::cacheSize;
+  using B::crc;
+  using B::cutValue;
+  using B::cyclicBufferPos;
+  using B::cyclicBufferSize;
+  using B::dst;
+  using B::dst_cap;
+  using B::finished;
+  using B::hash;
+  using B::hashMask;
+  using B::lc;
+  using B::longestMatchLength;
+  using B::low;
+  using B::lpMask;
+  using B::matches;
+  using B::nowPos64;
+  using B::numAvail;
+  using B::numFastBytes;
+  using B::numPairs;
+  using B::off;
+  using B::outPos;
+  using B::overflow;
+  using B::pbMask;
+  using B::probs;
+  using B::range;
+  using B::rep0;
+  using B::rep1;
+  using B::rep2;
+  using B::rep3;
+  using B::son;
+  using B::src;
+  using B::src_len;
+  using B::state;
+  using B::writeEndMark;
+
+  using B::avail;
+  using B::flush;
+  using B::read_match_distances;
+  using B::encode_bit;
+  using B::lit_next;
+  using B::lit_encode;
+  using B::get_optimum_fast;
+  using B::lit_encode_matched;
+  using B::rep;
+  using B::short_rep_next;
+  using B::len_encode;
+  using B::rep_next;
+  using B::match_next;
+  using B::get_pos_slot;
+  using B::tree_encode;
+  using B::len_to_pos_state;
+  using B::tree_reverse_encode;
+  using B::encode_direct_bits;
+
+  // LzmaEnc_CodeOneBlock(p, True, 1 << 16, 1 << 21).  The normal modes take
+  // LzmaEncT's code_block<true>; the fast path keeps its own text of
+  // code_one_block with the chunk limits in place of the 32 KiB progress step,
+  // always ending in Flush (the token coding in the middle is the same text),
+  // so that its kernel stays the code it was.
   LZENC_FN void code_chunk() {
-    uint32_t nowPos32 = nowPos64;
-    const uint32_t startPos32 = nowPos32;
+    if constexpr (kNormal) {
+      this->template code_block<true>();
+    } else {
+      uint32_t nowPos32 = nowPos64;
+      const uint32_t startPos32 = nowPos32;
 
-    if (nowPos64 == 0) {
-      uint32_t pairs;
-      if (avail() == 0) {
-        flush(nowPos32);
-        return;
+      if (nowPos64 == 0) {
+        uint32_t pairs;
+        if (avail() == 0) {
+          flush(nowPos32);
+          return;
+        }
+        read_match_distances(&pairs);
+        encode_bit(kIsMatch + state * 16, 0);
+        state = lit_next(state);
+        const uint32_t curByte = src[off - additionalOffset];
+        lit_encode(kLit, curByte);
+        additionalOffset--;
+        nowPos32++;
       }
-      read_match_distances(&pairs);
-      encode_bit(kIsMatch + state * 16, 0);
-      state = lit_next(state);
-      const uint32_t curByte = src[off - additionalOffset];
-      lit_encode(kLit, curByte);
-      additionalOffset--;
-      nowPos32++;
-    }
 
-    if (avail() != 0)
-      for (;;) {
-        uint32_t pos;
-        const uint32_t len = get_optimum_fast(&pos);
-        const uint32_t posState = nowPos32 & pbMask;
-        if (len == 1 && pos == 0xFFFFFFFFu) {
-          encode_bit(kIsMatch + state * 16 + posState, 0);
-          const uint8_t* data = src + off - additionalOffset;
-          const uint32_t curByte = *data;
-          const uint32_t lit =
-              kLit + (((nowPos32 & lpMask) << lc) + (uint32_t(*(data - 1)) >> (8 - lc))) * 0x300;
-          if (state < 7)
-            lit_encode(lit, curByte);
-          else
-            lit_encode_matched(lit, curByte, *(data - rep0 - 1));
-          state = lit_next(state);
-        } else {
-          encode_bit(kIsMatch + state * 16 + posState, 1);
-          if (pos < kNumReps) {
-            encode_bit(kIsRep + state, 1);
-            if (pos == 0) {
-              encode_bit(kIsRepG0 + state, 0);
-              encode_bit(kIsRep0Long + state * 16 + posState, (len == 1) ? 0 : 1);
-            } else {
-              const uint32_t distance = rep(pos);
-              encode_bit(kIsRepG0 + state, 1);
-              if (pos == 1)
-                encode_bit(kIsRepG1 + state, 0);
-              else {
-                encode_bit(kIsRepG1 + state, 1);
-                encode_bit(kIsRepG2 + state, pos - 2);
-                if (pos == 3) rep3 = rep2;
-                rep2 = rep1;
-              }
-              rep1 = rep0;
-              rep0 = distance;
-            }
-            if (len == 1)
-              state = short_rep_next(state);
-            else {
-              len_encode(kRepLenEnc, len - kMatchLenMin, posState);
-              state = rep_next(state);
-            }
+      if (avail() != 0)
+        for (;;) {
+          uint32_t pos;
+          const uint32_t len = get_optimum_fast(&pos);
+          const uint32_t posState = nowPos32 & pbMask;
+          if (len == 1 && pos == 0xFFFFFFFFu) {
+            encode_bit(kIsMatch + state * 16 + posState, 0);
+            const uint8_t* data = src + off - additionalOffset;
+            const uint32_t curByte = *data;
+            const uint32_t lit =
+                kLit + (((nowPos32 & lpMask) << lc) + (uint32_t(*(data - 1)) >> (8 - lc))) * 0x300;
+            if (state < 7)
+              lit_encode(lit, curByte);
+            else
+              lit_encode_matched(lit, curByte, *(data - rep0 - 1));
+            state = lit_next(state);
           } else {
-            encode_bit(kIsRep + state, 0);
-            state = match_next(state);
-            len_encode(kLenEnc, len - kMatchLenMin, posState);
-            pos -= kNumReps;
-            const uint32_t posSlot = get_pos_slot(pos);
-            tree_encode(kPosSlot + len_to_pos_state(len) * 64, 6, posSlot);
-            if (posSlot >= kStartPosModelIndex) {
-              const uint32_t footerBits = (posSlot >> 1) - 1;
-              const uint32_t base = (2 | (posSlot & 1)) << footerBits;
-              const uint32_t posReduced = pos - base;
-              if (posSlot < kEndPosModelIndex)
-                tree_reverse_encode(kPosEncoders + base - posSlot - 1, int(footerBits), posReduced);
-              else {
-                encode_direct_bits(posReduced >> kNumAlignBits, int(footerBits - kNumAlignBits));
-                tree_reverse_encode(kPosAlign, kNumAlignBits, posReduced & 15);
+            encode_bit(kIsMatch + state * 16 + posState, 1);
+            if (pos < kNumReps) {
+              encode_bit(kIsRep + state, 1);
+              if (pos == 0) {
+                encode_bit(kIsRepG0 + state, 0);
+                encode_bit(kIsRep0Long + state * 16 + posState, (len == 1) ? 0 : 1);
+              } else {
+                const uint32_t distance = rep(pos);
+                encode_bit(kIsRepG0 + state, 1);
+                if (pos == 1)
+                  encode_bit(kIsRepG1 + state, 0);
+                else {
+                  encode_bit(kIsRepG1 + state, 1);
+                  encode_bit(kIsRepG2 + state, pos - 2);
+                  if (pos == 3) rep3 = rep2;
+                  rep2 = rep1;
+                }
+                rep1 = rep0;
+                rep0 = distance;
               }
+              if (len == 1)
+                state = short_rep_next(state);
+              else {
+                len_encode(kRepLenEnc, len - kMatchLenMin, posState);
+                state = rep_next(state);
+              }
+            } else {
+              encode_bit(kIsRep + state, 0);
+              state = match_next(state);
+              len_encode(kLenEnc, len - kMatchLenMin, posState);
+              pos -= kNumReps;
+              const uint32_t posSlot = get_pos_slot(pos);
+              tree_encode(kPosSlot + len_to_pos_state(len) * 64, 6, posSlot);
+              if (posSlot >= kStartPosModelIndex) {
+                const uint32_t footerBits = (posSlot >> 1) - 1;
+                const uint32_t base = (2 | (posSlot & 1)) << footerBits;
+                const uint32_t posReduced = pos - base;
+                if (posSlot < kEndPosModelIndex)
+                  tree_reverse_encode(kPosEncoders + base - posSlot - 1, int(footerBits), posReduced);
+                else {
+                  encode_direct_bits(posReduced >> kNumAlignBits, int(footerBits - kNumAlignBits));
+                  tree_reverse_encode(kPosAlign, kNumAlignBits, posReduced & 15);
+                }
+              }
+              rep3 = rep2;
+              rep2 = rep1;
+              rep1 = rep0;
+              rep0 = pos;
             }
-            rep3 = rep2;
-            rep2 = rep1;
-            rep1 = rep0;
-            rep0 = pos;
+          }
+          additionalOffset -= len;
+          nowPos32 += len;
+          if (additionalOffset == 0) {
+            if (avail() == 0) break;
+            const uint32_t processed = nowPos32 - startPos32;
+            // RangeEnc_GetProcessed: the chunk's bytes written plus cacheSize
+            if (processed + kNumOpts + 300 >= kLzma2UnpackMax ||
+                outPos + cacheSize + kNumOpts * 2 >= kLzma2PackMax)
+              break;
           }
         }
-        additionalOffset -= len;
-        nowPos32 += len;
-        if (additionalOffset == 0) {
-          if (avail() == 0) break;
-          const uint32_t processed = nowPos32 - startPos32;
-          // RangeEnc_GetProcessed: the chunk's bytes written plus cacheSize
-          if (processed + kNumOpts + 300 >= kLzma2UnpackMax ||
-              outPos + cacheSize + kNumOpts * 2 >= kLzma2PackMax)
-            break;
-        }
-      }
-    nowPos64 += nowPos32 - startPos32;
-    flush(nowPos32);
+      nowPos64 += nowPos32 - startPos32;
+      flush(nowPos32);
+    
+    }
   }
+
 
   // One block: q has passed lzma2_check_params, the slice lzmaenc_init_slice.
   // {SZ_OK, bytes of all chunks} or {SZ_ERROR_OUTPUT_EOF, bytes of the whole
@@ -272,7 +344,7 @@ struct Lzma2Enc : LzmaEnc {
   // breaks); bytes in [dest_len, dst_cap_) are then unspecified.
   LZENC_FN Out encode_block(const uint8_t* src_, uint32_t src_len_, uint8_t* dst_,
                             uint64_t dst_cap_, const Params& q, uint8_t* slice, const Layout2& m,
-                            const uint32_t* crc_) {
+                            const uint32_t* crc_, const uint32_t* probPrices_ = nullptr) {
     src = src_;
     probs = reinterpret_cast<uint16_t*>(slice + m.l.probs);
     matches = reinterpret_cast<uint32_t*>(slice + m.l.matches);
@@ -296,6 +368,7 @@ struct Lzma2Enc : LzmaEnc {
     additionalOffset = 0;
     longestMatchLength = numPairs = numAvail = 0;
     nowPos64 = 0;
+    if constexpr (kNormal) this->setup_normal(q, slice, m.l, probPrices_);
     // Lzma2EncInt_Init
     const uint8_t lzmaProps = uint8_t((q.pb * 5 + q.lp) * 9 + q.lc);
     uint8_t* const cells = slice + m.l.probs;
@@ -330,6 +403,9 @@ struct Lzma2Enc : LzmaEnc {
       range = 0xFFFFFFFFu;
       cacheSize = 1;
       cache = 0;
+      // LzmaEnc_InitPrices (LzmaEnc.c:2139): every price table is rebuilt from
+      // the cells, so cells, reps and state are all a restore has to put back
+      if constexpr (kNormal) this->init_prices();
       const uint32_t before = nowPos64;
       code_chunk();
       uint32_t unpackSize = nowPos64 - before;
@@ -388,5 +464,7 @@ struct Lzma2Enc : LzmaEnc {
     return o;
   }
 };
+using Lzma2Enc = Lzma2EncT<false>;
+using Lzma2EncNormal = Lzma2EncT<true>;
 
 }  // namespace lzenc

@@ -1,4 +1,4 @@
-// lzma2enc_kernels.hip -- LZMA2 fast-mode block encoding for gfx950: one block
+// lzma2enc_kernels.hip -- LZMA2 block encoding for gfx950: one block
 // per lane (lzma2enc_device.h's chunk driver over lzmaenc_device.h's encoder),
 // and the compaction that turns the blocks' slots into one LZMA2 stream
 // without a visit to the host.
@@ -9,7 +9,13 @@
 //                            (it is written before it is read)
 //   lzma2enc_encode_kernel   lzmaenc_encode_kernel's geometry: one wave per
 //                            workgroup, `lanes` blocks per wave, the CRC table
-//                            in LDS, no synchronisation in the loop
+//                            in LDS, no synchronisation in the loop; mode 0
+//                            (the fast path) only
+//   lzma2enc_encode_normal_kernel  (lzma2enc_normal_kernels.hip) the same for the normal modes (the optimal
+//                            parser and / or Bt4: Lzma2EncNormal), ProbPrices
+//                            in LDS beside the CRC table; it walks the same
+//                            order and leaves mode-0 and rejected blocks to the
+//                            kernel above
 //   lzma2enc_scan_kernel     one workgroup: exclusive scan of the blocks'
 //                            dest_len, the first failed block, the total
 //   lzma2enc_compact_kernel  one workgroup per block gathers its bytes from its
@@ -61,6 +67,7 @@ __global__ void __launch_bounds__(64) lzma2enc_encode_kernel(
   lzenc::Out o;
   o.res = lzma2enc_check(d);
   o.dest_len = 0;
+  if (o.res == lzenc::kOk && d.mode != 0) return;  // lzma2enc_encode_normal_kernel's
   if (o.res == lzenc::kOk) {
     const lzenc::Params q = lzmaenc_params(d);
     const lzenc::Layout2 m = lzenc::lzma2enc_layout(q, d.src_len);
@@ -185,9 +192,9 @@ extern "C" int lzma2encgpu_launch(const LzmaEncGpuStreamDesc* d_descs, const uin
                                   uint32_t first, uint32_t count, uint32_t n,
                                   const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_ws,
                                   LzmaEncGpuResult* d_results, uint32_t lanes,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, uint32_t kernels) {
   if (count == 0) return 0;
-  if (lanes != 16 && lanes != 32 && lanes != 64) return -2;
+  if (lanes != 0 && lanes != 16 && lanes != 32 && lanes != 64) return -2;
   if (first > n || count > n - first) return -2;
   // at least ~4,096 workgroups of 256 for the clear, at most 64 parts a block
   uint32_t parts = (4096 + count - 1) / count;
@@ -198,10 +205,18 @@ extern "C" int lzma2encgpu_launch(const LzmaEncGpuStreamDesc* d_descs, const uin
   hipLaunchKernelGGL(lzma2enc_init_kernel, dim3(grid), dim3(kInitThreads), 0, stream, d_descs,
                      d_order, first, count, n, parts, d_ws);
   if (hipGetLastError() != hipSuccess) return -1;
-  const uint32_t groups = uint32_t((uint64_t(count) + lanes - 1) / lanes);
-  hipLaunchKernelGGL(lzma2enc_encode_kernel, dim3(groups), dim3(64), 0, stream, d_descs, d_order,
-                     first, count, n, lanes, d_src, d_dst, d_ws, d_results);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  if ((kernels & kLzmaEncKernelNormal) &&
+      lzma2encgpu_launch_normal(d_descs, d_order, first, count, n, d_src, d_dst, d_ws, d_results,
+                                lanes ? lanes : kLzmaEncLanesNormalDefault, stream) != 0)
+    return -1;
+  if (kernels & kLzmaEncKernelFast) {
+    const uint32_t lf = lanes ? lanes : kLzmaEncLanesDefault;
+    const uint32_t groups = uint32_t((uint64_t(count) + lf - 1) / lf);
+    hipLaunchKernelGGL(lzma2enc_encode_kernel, dim3(groups), dim3(64), 0, stream, d_descs, d_order,
+                       first, count, n, lf, d_src, d_dst, d_ws, d_results);
+    if (hipGetLastError() != hipSuccess) return -1;
+  }
+  return 0;
 }
 
 extern "C" int lzma2encgpu_launch_compact(const LzmaEncGpuStreamDesc* d_descs,

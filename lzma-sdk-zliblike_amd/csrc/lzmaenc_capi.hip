@@ -1,11 +1,14 @@
-// lzmaenc_capi.hip -- C ABI of the LZMA fast-mode batch encoder
+// lzmaenc_capi.hip -- C ABI of the LZMA batch encoder
 // (include/lzma_gpu.h): the props drop-ins, descriptor and workspace planning,
 // the device and host batch calls, and LzmaEncode / LzmaCompress as one-item
 // calls of the host form.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <vector>
 
 #include "../../include/lzma_gpu.h"
@@ -44,17 +47,33 @@ extern "C" UInt32 LzmaEncProps_GetDictSize(const CLzmaEncProps* props2) {
   return e.dictSize;
 }
 
-static const char kNotFastPath[] =
-    "LZMA encode: props normalise to the optimal parser (algo 1) or a bt match finder "
-    "(btMode 1); only the fast path (levels 0..4: algo 0, btMode 0) is built";
+// the process-wide mask: LZGPU_ENC_MODES (decimal) read once, then SetModes
+static std::atomic<uint32_t>& allowed_modes() {
+  static std::atomic<uint32_t> mask([] {
+    const char* v = getenv("LZGPU_ENC_MODES");
+    return v ? uint32_t(strtoul(v, nullptr, 10)) & 3u : 0u;
+  }());
+  return mask;
+}
+uint32_t lzmaenc_allowed_modes() { return allowed_modes().load(); }
+extern "C" unsigned LzmaEncGpu_SetModes(unsigned allowed) {
+  return allowed_modes().exchange(allowed & 3u);
+}
+extern "C" unsigned LzmaEncGpu_GetModes(void) { return lzmaenc_allowed_modes(); }
 
-extern "C" SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps* props, int writeEndMark,
-                                         LzmaEncGpuStreamDesc* desc, Byte props5[5]) {
-  const lzenc::EncProps e = to_enc(props);
-  lzenc::Params q;
-  const int32_t r = lzenc::params_from_props(&e, writeEndMark, &q);
-  if (r == lzenc::kErrUnsupported) set_error(kNotFastPath);
-  if (r != lzenc::kOk) return r;
+void lzmaenc_set_unsupported_error(const char* field) {
+  const std::string f(field ? field : "algo");
+  if (f == "numHashBytes")
+    set_error("LZMA encode: props field numHashBytes selects the Bt2 or Bt3 match finder; of the "
+              "bt finders only Bt4 (numHashBytes 4) is built");
+  else
+    set_error(("LZMA encode: props field " + f + " normalises to the optimal parser (algo 1) or "
+               "the Bt4 match finder (btMode 1), which the mode mask does not allow "
+               "(LzmaEncGpu_SetModes, LZGPU_ENC_MODES); mask 0 is the fast path alone "
+               "(levels 0..4: algo 0, btMode 0)").c_str());
+}
+
+static void fill_desc(LzmaEncGpuStreamDesc* desc, const lzenc::Params& q) {
   desc->dict_size = q.dict_size;
   desc->lc = q.lc;
   desc->lp = q.lp;
@@ -62,9 +81,26 @@ extern "C" SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps* props, int writeEn
   desc->fb = q.fb;
   desc->mc = q.mc;
   desc->write_end_mark = q.write_end_mark;
-  desc->reserved = 0;
+  desc->mode = lzenc::mode_of(q);
+}
+
+extern "C" SRes LzmaEncGpu_DescFromPropsEx(const CLzmaEncProps* props, int writeEndMark,
+                                           unsigned allowed, LzmaEncGpuStreamDesc* desc,
+                                           Byte props5[5]) {
+  const lzenc::EncProps e = to_enc(props);
+  lzenc::Params q;
+  const char* field = nullptr;
+  const int32_t r = lzenc::params_from_props_ex(&e, writeEndMark, allowed, &q, &field);
+  if (r == lzenc::kErrUnsupported) lzmaenc_set_unsupported_error(field);
+  if (r != lzenc::kOk) return r;
+  fill_desc(desc, q);
   lzenc::write_props5(q, props5);
   return SZ_OK;
+}
+
+extern "C" SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps* props, int writeEndMark,
+                                         LzmaEncGpuStreamDesc* desc, Byte props5[5]) {
+  return LzmaEncGpu_DescFromPropsEx(props, writeEndMark, lzmaenc_allowed_modes(), desc, props5);
 }
 
 extern "C" SRes LzmaEncGpu_PlanBatch(LzmaEncGpuStreamDesc* descs, size_t n, uint32_t* order,
@@ -78,7 +114,7 @@ extern "C" SRes LzmaEncGpu_PlanBatch(LzmaEncGpuStreamDesc* descs, size_t n, uint
       at += need;
     }
     if (workspace_bytes) *workspace_bytes = at;
-    if (order) longest_first(n, [&](uint32_t i) { return descs[i].src_len; }, order);
+    if (order) longest_first(n, [&](uint32_t i) { return lzmaenc_work(descs[i]); }, order);
     return SZ_OK;
   });
 }
@@ -88,8 +124,8 @@ extern "C" SRes LzmaEncGpu_EncodeBatch(const LzmaEncGpuStreamDesc* d_descs, cons
                                        LzmaEncGpuResult* d_results, unsigned lanes, void* stream) {
   if (!ensure_device()) return SZ_ERROR_FAIL;
   if (n > 0x7FFFFFFFull) return SZ_ERROR_PARAM;
-  if (lanes == LZMA_ENC_GPU_LANES_DEFAULT) lanes = kLzmaEncLanesDefault;
-  if (lanes != 16 && lanes != 32 && lanes != 64) return SZ_ERROR_PARAM;
+  if (lanes != LZMA_ENC_GPU_LANES_DEFAULT && lanes != 16 && lanes != 32 && lanes != 64)
+    return SZ_ERROR_PARAM;
   if (n == 0) return SZ_OK;
   if (lzmaencgpu_launch(d_descs, d_order, uint32_t(n), d_src, d_dst,
                         static_cast<uint8_t*>(d_workspace), d_results, lanes,
@@ -112,12 +148,14 @@ static SRes encode_batch_host(const LzmaEncGpuStreamDesc* descs, size_t n, const
   SRes r = b.lay_out(
       what, descs, n, src_size, dst_size, workspace_limit,
       [](const LzmaEncGpuStreamDesc& d) { return d.dst_cap; },
-      [](const LzmaEncGpuStreamDesc& d) { return d.src_len; }, lzmaenc_slice_bytes);
+      lzmaenc_work, lzmaenc_slice_bytes);
   if (r != SZ_OK) return r;
-  r = b.queue(what, in_launch_order(descs, b.plan), false, src, src_size,
-              one_item ? nullptr : dst, dst_size, [&](uint32_t lo, uint32_t cnt) {
+  const std::vector<LzmaEncGpuStreamDesc> d = in_launch_order(descs, b.plan);
+  r = b.queue(what, d, false, src, src_size, one_item ? nullptr : dst, dst_size,
+              [&](uint32_t lo, uint32_t cnt) {
                 return lzmaencgpu_launch(b.desc.p + lo, nullptr, cnt, b.src.p, b.dst.p, b.ws.p,
-                                         b.res.p + lo, kLzmaEncLanesDefault, nullptr);
+                                         b.res.p + lo, LZMA_ENC_GPU_LANES_DEFAULT, nullptr,
+                                         lzmaenc_kernels(d.data() + lo, cnt, lzmaenc_check));
               });
   if (r != SZ_OK || (r = b.wait_scattered(what, results)) != SZ_OK) return r;
   const size_t off = one_item ? size_t(descs[0].dst_off) : 0;
@@ -147,11 +185,13 @@ extern "C" SRes LzmaEncode(Byte* dest, SizeT* destLen, const Byte* src, SizeT sr
   // library does not encode
   const lzenc::EncProps e = to_enc(props);
   lzenc::Params q;
-  const int32_t pr = lzenc::params_from_props(&e, writeEndMark, &q);
+  const char* field = nullptr;
+  const int32_t pr =
+      lzenc::params_from_props_ex(&e, writeEndMark, lzmaenc_allowed_modes(), &q, &field);
   if (pr == lzenc::kErrParam) return SZ_ERROR_PARAM;
   if (*propsSize < LZMA_PROPS_SIZE) return SZ_ERROR_PARAM;
   if (pr == lzenc::kErrUnsupported) {
-    set_error(kNotFastPath);
+    lzmaenc_set_unsupported_error(field);
     return SZ_ERROR_UNSUPPORTED;
   }
   if (uint64_t(srcLen) >= (uint64_t(1) << 31)) {
@@ -165,13 +205,7 @@ extern "C" SRes LzmaEncode(Byte* dest, SizeT* destLen, const Byte* src, SizeT sr
   memset(&d, 0, sizeof(d));
   d.src_len = srcLen;
   d.dst_cap = *destLen;
-  d.dict_size = q.dict_size;
-  d.lc = q.lc;
-  d.lp = q.lp;
-  d.pb = q.pb;
-  d.fb = q.fb;
-  d.mc = q.mc;
-  d.write_end_mark = q.write_end_mark;
+  fill_desc(&d, q);
   LzmaEncGpuResult r;
   r.res = SZ_ERROR_FAIL;
   r.dest_len = 0;

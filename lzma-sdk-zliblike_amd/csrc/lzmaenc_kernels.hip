@@ -1,4 +1,4 @@
-// lzmaenc_kernels.hip -- LZMA fast-mode batch encoding for gfx950: one stream
+// lzmaenc_kernels.hip -- LZMA batch encoding for gfx950: one stream
 // per lane, lzmaenc_device.h's encoder with its range-coder and parser state in
 // registers and its tables (probability cells, `matches`, hash, `son` ring) in
 // the stream's workspace slice.  The work is pointer chasing through the hash
@@ -13,7 +13,16 @@
 //                          table (1 KiB) is built in LDS before the loop; the
 //                          encode loop has no block-wide synchronisation, and a
 //                          lane whose stream is rejected, empty or finished just
-//                          returns.
+//                          returns.  Mode 0 (the fast path) only: a lane whose
+//                          stream has a normal mode returns before it touches
+//                          memory.
+//   lzmaenc_encode_normal_kernel  (lzmaenc_normal_kernels.hip) the same geometry for the normal modes (the
+//                          optimal parser and / or Bt4: LzmaEncNormal), with
+//                          ProbPrices (512 bytes) in LDS beside the CRC table.
+//                          It walks the same order and leaves mode-0 and
+//                          rejected streams to the kernel above; a workgroup
+//                          without a stream of its own returns before it builds
+//                          the tables.
 #include <hip/hip_runtime.h>
 
 #include "../../include/lzma_gpu.h"
@@ -56,6 +65,7 @@ __global__ void __launch_bounds__(64) lzmaenc_encode_kernel(
   lzenc::Out o;
   o.res = lzmaenc_check(d);
   o.dest_len = 0;
+  if (o.res == lzenc::kOk && d.mode != 0) return;  // lzmaenc_encode_normal_kernel's
   if (o.res == lzenc::kOk) {
     const lzenc::Params q = lzmaenc_params(d);
     const lzenc::Layout l = lzenc::lzmaenc_layout(q, d.src_len);
@@ -88,12 +98,22 @@ extern "C" int lzmaencgpu_launch_init(const LzmaEncGpuStreamDesc* d_descs, uint3
 
 extern "C" int lzmaencgpu_launch(const LzmaEncGpuStreamDesc* d_descs, const uint32_t* d_order,
                                  uint32_t n, const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_ws,
-                                 LzmaEncGpuResult* d_results, uint32_t lanes, hipStream_t stream) {
+                                 LzmaEncGpuResult* d_results, uint32_t lanes, hipStream_t stream,
+                                 uint32_t kernels) {
   if (n == 0) return 0;
-  if (lanes != 16 && lanes != 32 && lanes != 64) return -2;
+  if (lanes != 0 && lanes != 16 && lanes != 32 && lanes != 64) return -2;
   if (lzmaencgpu_launch_init(d_descs, n, d_ws, stream) != 0) return -1;
-  const uint32_t groups = uint32_t((uint64_t(n) + lanes - 1) / lanes);
-  hipLaunchKernelGGL(lzmaenc_encode_kernel, dim3(groups), dim3(64), 0, stream, d_descs, d_order, n,
-                     lanes, d_src, d_dst, d_ws, d_results);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  // the normal modes first: they come first in the order and take longest
+  if ((kernels & kLzmaEncKernelNormal) &&
+      lzmaencgpu_launch_normal(d_descs, d_order, n, d_src, d_dst, d_ws, d_results,
+                               lanes ? lanes : kLzmaEncLanesNormalDefault, stream) != 0)
+    return -1;
+  if (kernels & kLzmaEncKernelFast) {
+    const uint32_t lf = lanes ? lanes : kLzmaEncLanesDefault;
+    const uint32_t groups = uint32_t((uint64_t(n) + lf - 1) / lf);
+    hipLaunchKernelGGL(lzmaenc_encode_kernel, dim3(groups), dim3(64), 0, stream, d_descs, d_order,
+                       n, lf, d_src, d_dst, d_ws, d_results);
+    if (hipGetLastError() != hipSuccess) return -1;
+  }
+  return 0;
 }

@@ -506,8 +506,9 @@ SRes launch_lzma(const KindBatch<LzmaEncGpuStreamDesc>& b, DevArr<LzmaEncGpuStre
                  const uint8_t* src, uint8_t* dst, uint8_t* ws, LzmaEncGpuResult* res,
                  uint64_t* launches) {
   return launch_kind("7z write: LZMA encode", b, g, launches, [&](uint32_t lo, uint32_t cnt) {
-    return lzmaencgpu_launch(g.p + lo, nullptr, cnt, src, dst, ws, res + lo, kLzmaEncLanesDefault,
-                             nullptr);
+    return lzmaencgpu_launch(g.p + lo, nullptr, cnt, src, dst, ws, res + lo,
+                             LZMA_ENC_GPU_LANES_DEFAULT, nullptr,
+                             lzmaenc_kernels(b.d.data() + lo, cnt, lzmaenc_check));
   });
 }
 SRes launch_lzma2(const KindBatch<LzmaEncGpuStreamDesc>& b, DevArr<LzmaEncGpuStreamDesc>& g,
@@ -515,7 +516,8 @@ SRes launch_lzma2(const KindBatch<LzmaEncGpuStreamDesc>& b, DevArr<LzmaEncGpuStr
                   uint64_t* launches) {
   return launch_kind("7z write: LZMA2 encode", b, g, launches, [&](uint32_t lo, uint32_t cnt) {
     return lzma2encgpu_launch(g.p, nullptr, lo, cnt, uint32_t(b.d.size()), src, dst, ws, res,
-                              kLzmaEncLanesDefault, nullptr);
+                              LZMA_ENC_GPU_LANES_DEFAULT, nullptr,
+                              lzmaenc_kernels(b.d.data() + lo, cnt, lzma2enc_check));
   });
 }
 SRes launch_ppmd(const KindBatch<Ppmd7GpuEncDesc>& b, DevArr<Ppmd7GpuEncDesc>& g,

@@ -35,6 +35,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LEVEL = 1
+DICT = 0   # --level 5 and up: the block size (the hash is sized by the dictionary)
 MIB = 1 << 20
 
 
@@ -58,7 +59,7 @@ def ref_lib():
 def ref_block(lib, addr, length, dst, cap):
     dl = ctypes.c_size_t(cap)
     prop = ctypes.c_ubyte(0)
-    res = lib.ref_lzma2_encode(dst, ctypes.byref(dl), addr, length, LEVEL, 0, -1, -1, -1, 0,
+    res = lib.ref_lzma2_encode(dst, ctypes.byref(dl), addr, length, LEVEL, min(DICT, length) if DICT else 0, -1, -1, -1, 0,
                                ctypes.byref(prop))
     assert res == 0, res
     return dl.value
@@ -106,7 +107,7 @@ def timed(torch, fn, reps):
 
 
 def gpu_setup(L, torch, np, buf, total, block):
-    r, proto, prop = L.enc2_desc_from_props(L.enc2_props(LEVEL))
+    r, proto, prop = L.enc2_desc_from_props(L.enc2_props(LEVEL, DICT))
     assert r == 0
     n = (total + block - 1) // block
     cap = L.block_bound(block)
@@ -191,7 +192,7 @@ def run_table(a, L, torch, np, native, emit):
     warm = ctypes.create_string_buffer(2 * MIB)
     prop = ctypes.c_ubyte(0)
     assert L.lib.LzmaGpu_Lzma2EncodeHost(warm, ctypes.byref(dl), small, MIB,
-                                         ctypes.byref(L.enc2_props(LEVEL, block_size=65536)),
+                                         ctypes.byref(L.enc2_props(LEVEL, DICT, block_size=65536)),
                                          ctypes.byref(prop)) == 0, L.last_error()
     for mib in (int(x) for x in a.sizes.split(",")):
         total = mib * MIB
@@ -217,7 +218,7 @@ def run_table(a, L, torch, np, native, emit):
                       ratio=round(packed / total, 4), verified_blocks=checked))
             del g
             torch.cuda.empty_cache()
-            props = L.enc2_props(LEVEL, block_size=block)
+            props = L.enc2_props(LEVEL, DICT, block_size=block)
 
             def host_lzma2():
                 dl = ctypes.c_size_t(len(dest))
@@ -289,7 +290,14 @@ def main():
     ap.add_argument("--chunk-cost", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--level", type=int, default=1,
+                    help="5 and up: the optimal parser and Bt4, modes switched on for the run, "
+                         "dictionary = the smallest block size")
     a = ap.parse_args()
+    global LEVEL, DICT
+    LEVEL = a.level
+    if LEVEL >= 5:
+        DICT = min(int(x) for x in a.blocks.split(","))
     import numpy as np
     import torch
     sys.path.insert(0, HERE)
@@ -298,6 +306,8 @@ def main():
     import native
     if L.device_count() <= 0:
         raise SystemExit("lzma2enc_bench: no HIP device: " + L.last_error())
+    if LEVEL >= 5:
+        L.enc_set_modes(L.ENC_MODE_OPTIMAL | L.ENC_MODE_BT4)
     path = a.out or os.path.join(ROOT, "profiles", "lzma2enc",
                                  "chunk_cost.jsonl" if a.chunk_cost else "bench.jsonl")
     os.makedirs(os.path.dirname(path), exist_ok=True)

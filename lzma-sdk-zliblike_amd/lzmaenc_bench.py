@@ -1,7 +1,10 @@
 """Throughput of LzmaEncGpu_EncodeBatch (its own script; bench.py measures the
 LZMA decode flagship and is not involved).
 
-Level 1 with default props (64 KiB dictionary, lc3 lp0 pb2, fb 32, mc 16) on
+Level 1 with default props (64 KiB dictionary, lc3 lp0 pb2, fb 32, mc 16), or
+--level N (5 and up: the optimal parser and Bt4, with the modes switched on for
+the run and, unless --dict is given, a dictionary of the stream's size, since
+the hash is sized by the dictionary) on
 the synthetic generator's English-like text (csrc/synth.c), every stream with
 its own seed: replicas would flatter the hash and L2 behaviour.  Shapes:
 64 / 1,024 / 4,096 / 65,536 streams of 4 KiB, 4,096 of 64 KiB, one of 1 MiB.
@@ -31,6 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SHAPES = ((64, 4096), (1024, 4096), (4096, 4096), (65536, 4096), (4096, 65536), (1, 1 << 20))
 LEVEL = 1
+DICT = 0
 
 
 def make_streams(n, length):
@@ -43,7 +47,7 @@ def make_streams(n, length):
 
 def ref_encode_one(lib, base, length, dst, cap, props5):
     dl = ctypes.c_size_t(cap)
-    res = lib.ref_lzma_encode(dst, ctypes.byref(dl), base, length, LEVEL, 0, -1, -1, -1, -1, 0,
+    res = lib.ref_lzma_encode(dst, ctypes.byref(dl), base, length, LEVEL, DICT, -1, -1, -1, -1, 0,
                               props5)
     assert res == 0, res
     return dl.value
@@ -83,8 +87,8 @@ def cpu_leg(buf, n, length, threads):
 
 
 def gpu_setup(L, torch, np, buf, n, length):
-    r, proto, props5 = L.enc_desc_from_props(L.enc_props(LEVEL))
-    assert r == 0
+    r, proto, props5 = L.enc_desc_from_props(L.enc_props(LEVEL, DICT))
+    assert r == 0, L.last_error()
     cap = length + length // 2 + 1024
     descs = (L.EncStreamDesc * n)()
     for i in range(n):
@@ -168,7 +172,12 @@ def main():
     ap.add_argument("--ab", action="store_true", help="streams-per-wave A/B instead of the table")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--level", type=int, default=1)
+    ap.add_argument("--dict", type=int, default=0,
+                    help="dictSize; 0 = the level's default below level 5, the stream size from 5 up")
     a = ap.parse_args()
+    global LEVEL, DICT
+    LEVEL = a.level
     import numpy as np
     import torch
     sys.path.insert(0, HERE)
@@ -180,6 +189,8 @@ def main():
     path = a.out or os.path.join(ROOT, "profiles", "lzmaenc",
                                  "lanes_ab.jsonl" if a.ab else "bench.jsonl")
     os.makedirs(os.path.dirname(path), exist_ok=True)
+    if LEVEL >= 5:
+        L.enc_set_modes(L.ENC_MODE_OPTIMAL | L.ENC_MODE_BT4)
     with open(path, "a") as out:
         def emit(row):
             line = json.dumps(row)
@@ -188,7 +199,10 @@ def main():
             out.flush()
         for shape in a.shapes.split(","):
             n, length = (int(x) for x in shape.split("x"))
+            DICT = a.dict or (max(length, 4096) if LEVEL >= 5 else 0)
             tag = dict(level=LEVEL, streams=n, stream_bytes=length)
+            if DICT:
+                tag["dict_size"] = DICT
             mb = n * length / 1e6
             buf = make_streams(n, length)
             g = gpu_setup(L, torch, np, buf, n, length)

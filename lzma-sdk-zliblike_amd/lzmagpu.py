@@ -257,7 +257,7 @@ class EncStreamDesc(ctypes.Structure):
                 ("ws_off", ctypes.c_uint64), ("dict_size", ctypes.c_uint32),
                 ("lc", ctypes.c_uint32), ("lp", ctypes.c_uint32), ("pb", ctypes.c_uint32),
                 ("fb", ctypes.c_uint32), ("mc", ctypes.c_uint32),
-                ("write_end_mark", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("write_end_mark", ctypes.c_uint32), ("mode", ctypes.c_uint32)]
 
 
 class EncResult(ctypes.Structure):
@@ -450,6 +450,14 @@ _sig = {
     "LzmaEncProps_GetDictSize": (ctypes.c_uint32, [ctypes.POINTER(CLzmaEncProps)]),
     "LzmaEncGpu_DescFromProps": (ctypes.c_int, [ctypes.POINTER(CLzmaEncProps), ctypes.c_int,
                                                 ctypes.POINTER(EncStreamDesc), ctypes.c_char_p]),
+    "LzmaEncGpu_DescFromPropsEx": (ctypes.c_int, [ctypes.POINTER(CLzmaEncProps), ctypes.c_int,
+                                                  ctypes.c_uint, ctypes.POINTER(EncStreamDesc),
+                                                  ctypes.c_char_p]),
+    "LzmaEncGpu_SetModes": (ctypes.c_uint, [ctypes.c_uint]),
+    "LzmaEncGpu_GetModes": (ctypes.c_uint, []),
+    "Lzma2EncGpu_DescFromPropsEx": (ctypes.c_int, [ctypes.POINTER(CLzma2EncProps), ctypes.c_uint,
+                                                   ctypes.POINTER(EncStreamDesc),
+                                                   ctypes.POINTER(ctypes.c_ubyte)]),
     "LzmaEncGpu_PlanBatch": (ctypes.c_int, [ctypes.POINTER(EncStreamDesc), ctypes.c_size_t, _P,
                                             ctypes.POINTER(ctypes.c_uint64)]),
     "LzmaEncGpu_EncodeBatch": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P,
@@ -1305,6 +1313,28 @@ def enc_desc_from_props(props, end_mark=False):
     return r, d, props5.raw
 
 
+ENC_MODE_OPTIMAL, ENC_MODE_BT4 = 1, 2
+
+
+def enc_set_modes(allowed):
+    """LzmaEncGpu_SetModes: the process-wide mask of normal modes (ENC_MODE_*)
+    that the props entry points may select; returns the previous mask."""
+    return _lib.LzmaEncGpu_SetModes(allowed)
+
+
+def enc_get_modes():
+    return _lib.LzmaEncGpu_GetModes()
+
+
+def enc_desc_from_props_ex(props, allowed, end_mark=False):
+    """LzmaEncGpu_DescFromPropsEx: (res, EncStreamDesc, props5)."""
+    d = EncStreamDesc()
+    props5 = ctypes.create_string_buffer(5)
+    r = _lib.LzmaEncGpu_DescFromPropsEx(ctypes.byref(props), 1 if end_mark else 0, allowed,
+                                        ctypes.byref(d), props5)
+    return r, d, props5.raw
+
+
 def enc_plan(descs, n):
     """LzmaEncGpu_PlanBatch: fills descs[i].ws_off; (res, order, workspace_bytes)."""
     order = (ctypes.c_uint32 * max(n, 1))()
@@ -1400,6 +1430,15 @@ def enc2_desc_from_props(props):
     d = EncStreamDesc()
     prop = ctypes.c_ubyte(0)
     r = _lib.Lzma2EncGpu_DescFromProps(ctypes.byref(props), ctypes.byref(d), ctypes.byref(prop))
+    return r, d, prop.value
+
+
+def enc2_desc_from_props_ex(props, allowed):
+    """Lzma2EncGpu_DescFromPropsEx: (res, EncStreamDesc, prop byte)."""
+    d = EncStreamDesc()
+    prop = ctypes.c_ubyte(0)
+    r = _lib.Lzma2EncGpu_DescFromPropsEx(ctypes.byref(props), allowed, ctypes.byref(d),
+                                         ctypes.byref(prop))
     return r, d, prop.value
 
 
