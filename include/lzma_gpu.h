@@ -32,6 +32,13 @@
  *       LzmaEncProps_GetDictSize replaces LzmaEnc.h:35 / LzmaEnc.c:76-81
  *       LzmaEncode              replaces LzmaEnc.h:72-74 / LzmaEnc.c:2248-2268
  *       LzmaCompress            replaces LzmaLib.h:98-107 / LzmaLib.c:15-38
+ *       LzmaEnc_Create          replaces LzmaEnc.h:52 / LzmaEnc.c:1700-1707
+ *       LzmaEnc_Destroy         replaces LzmaEnc.h:53 / LzmaEnc.c:1727-1731
+ *       LzmaEnc_SetProps        replaces LzmaEnc.h:54 / LzmaEnc.c:391-443
+ *       LzmaEnc_WriteProperties replaces LzmaEnc.h:55 / LzmaEnc.c:2191-2218
+ *       LzmaEnc_Encode          replaces LzmaEnc.h:56-57 / LzmaEnc.c:2184-2189
+ *       LzmaEnc_MemEncode       replaces LzmaEnc.h:58-59 / LzmaEnc.c:2220-2246
+ *                               (differences: at their declarations below)
  *       Lzma2EncProps_Init      replaces Lzma2Enc.h:21 / Lzma2Enc.c:168-174
  *       Lzma2EncProps_Normalize replaces Lzma2Enc.h:22 / Lzma2Enc.c:176-234
  *       Lzma2Enc_Create         replaces Lzma2Enc.h:38 / Lzma2Enc.c:367-387
@@ -1087,6 +1094,141 @@ int LzmaCompress(unsigned char *dest, size_t *destLen, const unsigned char *src,
                  unsigned char *outProps, size_t *outPropsSize, int level, unsigned dictSize,
                  int lc, int lp, int pb, int fb, int numThreads);
 
+/* ---------------------------------------------------------------- LZMA encoder sessions */
+
+/* A device-resident fast-mode encoder that takes its stream in pieces: the
+ * encoder's counterpart of LzmaGpuSession.  The caller appends plain bytes to
+ * src, raises src_len and advances every session of a batch by one round of
+ * launches (LzmaEncGpu_SessionEncodeBatch).  After the call with finish == 1,
+ * dst[0, out_pos), res and out_pos are LzmaEncode's dest, result and *destLen
+ * over the whole input and a buffer of dst_cap bytes, whatever the piece sizes
+ * were.  Mode 0 only (levels 0..4: algo 0, btMode 0).
+ *
+ * Per call the caller sets src_len (bytes of src valid so far; never lower than
+ * before, at most src_cap), finish and in_budget, and reads res, status, in_pos
+ * and out_pos.  src is append-only and contiguous for the session's life: bytes
+ * below src_len stay where they are (the buffer may move between rounds if its
+ * content moves with it).  dst[prev out_pos, out_pos) are the call's new bytes;
+ * bytes below out_pos are final.
+ *
+ * A call that is not the last starts a token only while at least
+ * LZMA_ENC_GPU_SESSION_HOLD supplied bytes lie ahead of it (every
+ * "bytes left" the one-shot encoder looks at is then at its clamp).  So after a
+ * call with finish == 0 that ended with status NEEDS_INPUT,
+ * src_len - in_pos < LZMA_ENC_GPU_SESSION_HOLD, and a stream shorter than the
+ * hold emits nothing before its final call.
+ *   status NEEDS_INPUT  everything the hold allows is encoded
+ *          BUDGET       in_budget was reached: work is left, call again
+ *          FINISHED     the stream is complete (res SZ_OK), did not fit (res
+ *                       SZ_ERROR_OUTPUT_EOF: out_pos == dst_cap, dst holds the
+ *                       first dst_cap bytes of the full stream) or the record
+ *                       was refused (SZ_ERROR_PARAM / SZ_ERROR_UNSUPPORTED:
+ *                       props, src_cap >= 2^31, src_len above src_cap or below
+ *                       in_pos, ws not 16-byte aligned).  Later calls change
+ *                       nothing.
+ * in_budget: the call ends at the encoder's first 32 KiB progress step at or
+ * after that many input bytes (0 = no bound), which bounds a round's launch. */
+#define LZMA_ENC_GPU_SESSION_HOLD 546u   /* 2 * LZMA_MATCH_LEN_MAX */
+#define LZMA_ENC_GPU_SESSION_NEEDS_INPUT 0
+#define LZMA_ENC_GPU_SESSION_FINISHED 1
+#define LZMA_ENC_GPU_SESSION_BUDGET 2
+
+typedef struct LzmaEncGpuSession {   /* 200 bytes */
+  const Byte *src;       /* device: the plain stream so far */
+  Byte *dst;             /* device: the output */
+  void *ws;              /* device: LzmaEncGpu_SessionWorkspaceBytes() bytes, 16-byte aligned */
+  uint64_t src_cap;      /* room of src, below 2^31 */
+  uint64_t dst_cap;      /* room of dst */
+  uint64_t src_len;      /* this call: bytes of src valid so far */
+  uint64_t in_budget;    /* this call: input bytes to encode at most; 0 = no bound */
+  uint64_t in_pos;       /* result: input bytes encoded so far */
+  uint64_t out_pos;      /* result: final bytes in dst */
+  uint32_t dict_size, lc, lp, pb, fb, mc, write_end_mark;   /* normalised props */
+  uint32_t finish;       /* this call: src_len is the whole stream */
+  int32_t res, status;   /* results */
+  /* the encoder between calls: set by LzmaEncGpu_SessionInit, then the device's */
+  uint32_t needs_init, finished, overflow;
+  uint32_t off, cyclic_pos, longest_match_length, num_pairs, num_avail, additional_offset;
+  uint32_t reps[4], state, range, cache, cache_size;
+  uint32_t _pad;
+  uint64_t low, out_total;
+} LzmaEncGpuSession;
+
+/* Host only.  Bytes of a session's workspace slice: the probability cells, the
+ * `matches` array, the hash (sized by dictSize, as in LzmaEncGpu_PlanBatch) and
+ * the `son` ring sized by min(dictSize, src_cap) + 1; a multiple of 256.  0 for
+ * props LzmaEncGpu_SessionInit refuses or src_cap >= 2^31. */
+uint64_t LzmaEncGpu_SessionWorkspaceBytes(const CLzmaEncProps *props, uint64_t src_cap);
+/* Host only.  LzmaEncGpu_DescFromProps' checks and results over *props
+ * (SZ_ERROR_PARAM; SZ_ERROR_UNSUPPORTED for props that normalise to a normal
+ * mode whatever LzmaEncGpu_SetModes says, with LzmaGpu_LastError() naming the
+ * field, and for src_cap >= 2^31), then binds the caller's device buffers and
+ * marks the slice as needing initialisation: the first round in which the
+ * session has work clears its hash and sets its cells.  *s is written only on
+ * SZ_OK, where props5 holds LzmaEnc_WriteProperties' 5 bytes. */
+SRes LzmaEncGpu_SessionInit(LzmaEncGpuSession *s, const CLzmaEncProps *props, int writeEndMark,
+                            const Byte *d_src, uint64_t src_cap, Byte *d_dst, uint64_t dst_cap,
+                            void *d_workspace, Byte props5[5]);
+/* Bytes of d_scratch for a round over n sessions: two counters and two index
+ * lists (the sessions with work, and those of them whose slice needs
+ * initialising). */
+size_t LzmaEncGpu_SessionScratchBytes(size_t n);
+/* One call per session, all in one round of launches on `stream`: a list pass
+ * compacts the indices of the sessions with work (not finished, and finish set
+ * or src_len - in_pos >= LZMA_ENC_GPU_SESSION_HOLD) into d_scratch, the whole
+ * grid initialises the slices that need it, and one lane per listed session
+ * encodes (lanes per 64-lane wave: 64, 32, 16 or LZMA_ENC_GPU_LANES_DEFAULT).
+ * Waves past the list's end return at once, and a session without work is not
+ * read beyond its record nor written at all.  d_scratch[0] (uint32_t) is the
+ * number of sessions the round worked on.  No allocation, no synchronisation;
+ * n == 0 is a no-op.  SZ_ERROR_FAIL without a device, SZ_ERROR_PARAM for n above
+ * 2^31 - 1 or an unknown lanes value. */
+SRes LzmaEncGpu_SessionEncodeBatch(LzmaEncGpuSession *d_sessions, size_t n, void *d_scratch,
+                                   unsigned lanes, void *stream);
+/* The round's first launch alone (what lzmaenc_session_bench.py times): clears
+ * the two counters and compacts the lists into d_scratch. */
+SRes LzmaEncGpu_SessionListPass(const LzmaEncGpuSession *d_sessions, size_t n, void *d_scratch,
+                                void *stream);
+
+/* LzmaEnc.h:38-59: the handle API the reference's `lzma e` is written
+ * against, over one session.  LzmaEnc_Encode gathers inStream's reads into
+ * pieces (a piece is complete at 4 KiB, at most 1 MiB, or at the stream's end),
+ * appends each to a device buffer that starts at 1 MiB and doubles when full (a
+ * new allocation and a device-to-device copy of the stream so far; dst and,
+ * while the ring is sized by the source, the workspace slice grow with it),
+ * advances the session once per piece and writes each round's new bytes to
+ * outStream; a short write is SZ_ERROR_WRITE, a read error is returned as
+ * it is.  progress is called once per round with (in_pos, out_pos), not every
+ * 32 KiB; non-zero is SZ_ERROR_PROGRESS.  Props that select a normal mode: with
+ * the modes mask admitting them the stream is read to its end and encoded by
+ * LzmaEncode; otherwise SZ_ERROR_UNSUPPORTED, from SetProps already.
+ * LzmaEnc_MemEncode is LzmaEncode with the handle's props.  alloc only holds
+ * the handle. */
+#ifndef __7Z_TYPES_H
+typedef struct {   /* Types.h:137-160 */
+  SRes (*Read)(void *p, void *buf, size_t *size);
+  /* if (input(*size) != 0 && output(*size) == 0) means end_of_stream.
+     (output(*size) < input(*size)) is allowed */
+} ISeqInStream;
+typedef struct {
+  size_t (*Write)(void *p, const void *buf, size_t size);
+  /* Returns: result - the number of actually written bytes.
+     (result < size) means error */
+} ISeqOutStream;
+#endif
+#ifndef __LZMA_ENC_H
+typedef void *CLzmaEncHandle;
+#endif
+CLzmaEncHandle LzmaEnc_Create(ISzAlloc *alloc);
+void LzmaEnc_Destroy(CLzmaEncHandle p, ISzAlloc *alloc, ISzAlloc *allocBig);
+SRes LzmaEnc_SetProps(CLzmaEncHandle p, const CLzmaEncProps *props);
+SRes LzmaEnc_WriteProperties(CLzmaEncHandle p, Byte *properties, SizeT *size);
+SRes LzmaEnc_Encode(CLzmaEncHandle p, ISeqOutStream *outStream, ISeqInStream *inStream,
+                    ICompressProgress *progress, ISzAlloc *alloc, ISzAlloc *allocBig);
+SRes LzmaEnc_MemEncode(CLzmaEncHandle p, Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
+                       int writeEndMark, ICompressProgress *progress, ISzAlloc *alloc,
+                       ISzAlloc *allocBig);
+
 /* ---------------------------------------------------------------- LZMA2 and xz writers */
 
 /* LZMA2 in the reference's multi-threaded layout (Lzma2Enc.c:310-361): the
@@ -1116,18 +1258,6 @@ typedef struct {   /* 64 bytes, Lzma2Enc.h:13-19 */
   int numTotalThreads;
 } CLzma2EncProps;
 typedef void *CLzma2EncHandle;
-#endif
-#ifndef __7Z_TYPES_H
-typedef struct {   /* Types.h:137-160 */
-  SRes (*Read)(void *p, void *buf, size_t *size);
-  /* if (input(*size) != 0 && output(*size) == 0) means end_of_stream.
-     (output(*size) < input(*size)) is allowed */
-} ISeqInStream;
-typedef struct {
-  size_t (*Write)(void *p, const void *buf, size_t size);
-  /* Returns: result - the number of actually written bytes.
-     (result < size) means error */
-} ISeqOutStream;
 #endif
 
 /* Lzma2Enc.c:168-234, of a build with threads (NUM_MT_CODER_THREADS_MAX 32) */

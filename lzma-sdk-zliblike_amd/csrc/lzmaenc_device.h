@@ -137,6 +137,46 @@ LZENC_HD int32_t check_params(const Params& q, uint64_t src_len) {
   return kOk;
 }
 
+// Encoder sessions (LzmaEncT<false>::session_call).  A call that is not the
+// last starts a token only while this many supplied bytes lie ahead of it.
+constexpr uint32_t kSessionHold = 2 * kMatchLenMax;
+constexpr int32_t kSessionNeedsInput = 0, kSessionFinished = 1, kSessionBudget = 2;
+// what a call ends a session with before touching memory: the props, the
+// append-only source (src_len within src_cap, never behind what is encoded),
+// the slice's alignment
+template <class S>
+LZENC_HD Params session_params(const S& s) {
+  Params q;
+  q.dict_size = s.dict_size;
+  q.lc = s.lc;
+  q.lp = s.lp;
+  q.pb = s.pb;
+  q.fb = s.fb;
+  q.mc = s.mc;
+  q.write_end_mark = s.write_end_mark;
+  return q;
+}
+template <class S>
+LZENC_HD int32_t session_check(const S& s) {
+  const int32_t r = check_params(session_params(s), s.src_cap);
+  if (r != kOk) return r;
+  if (s.src_len > s.src_cap || s.src_len < s.in_pos) return kErrParam;
+  return (uint64_t(reinterpret_cast<uintptr_t>(s.ws)) & 15u) ? kErrParam : kOk;
+}
+// whether a round has anything to do for the session: the list pass's test.  A
+// record session_check refuses has work once: the lane that ends it.
+template <class S>
+LZENC_HD bool session_has_work(const S& s, uint32_t hold) {
+  if (s.finished) return false;
+  if (session_check(s) != kOk) return true;
+  return s.finish != 0 || s.src_len - s.in_pos >= hold;
+}
+// and whether the round has to initialise its slice first
+template <class S>
+LZENC_HD bool session_wants_init(const S& s, uint32_t hold) {
+  return s.needs_init != 0 && session_has_work(s, hold) && session_check(s) == kOk;
+}
+
 // MatchFinder_Create's hashMask for numHashBytes == 4 (LzFind.c:200-215)
 LZENC_HD uint32_t hash_mask(uint32_t dict_size) {
   uint32_t hs = dict_size - 1;
@@ -1468,14 +1508,25 @@ struct LzmaEncT {
   // step every 32 KiB.  kLimits == true is LZMA2's (p, True, 1 << 16, 1 << 21):
   // the chunk limits in place of the step, always ending in Flush, and no
   // CheckErrors on entry (the caller has just reset the output).
+  //
+  // kHold == true is a session's call (session_call below): src_len is what has
+  // been supplied so far, and unless `finish` is set a token starts only while
+  // src_len - nowPos >= hold, so that every "bytes left" the finder and the
+  // parser look at during the token is at its clamp.  The block then returns
+  // with the state as it stands -- additionalOffset may be 1, a literal whose
+  // successor's matches are already read -- and a later call goes on from
+  // there.  The other instantiations are the text they were.
   LZENC_FN void code_one_block() { code_block<false>(); }
-  template <bool kLimits>
-  LZENC_FN void code_block() {
+  template <bool kLimits, bool kHold = false>
+  LZENC_FN void code_block(uint32_t finish = 1, uint32_t hold = 0) {
     if constexpr (!kLimits) {
       if (check_errors()) return;
     }
     uint32_t nowPos32 = nowPos64;
     const uint32_t startPos32 = nowPos32;
+    if constexpr (kHold) {
+      if (!finish && src_len - nowPos32 < hold) return;
+    }
 
     if (nowPos64 == 0) {
       uint32_t pairs;
@@ -1492,8 +1543,16 @@ struct LzmaEncT {
       nowPos32++;
     }
 
-    if (avail() != 0)
+    bool more = avail() != 0;
+    if constexpr (kHold) more = more || additionalOffset != 0;  // a token read ahead is pending
+    if (more)
       for (;;) {
+        if constexpr (kHold) {
+          if (!finish && src_len - nowPos32 < hold) {
+            nowPos64 += nowPos32 - startPos32;
+            return;
+          }
+        }
         uint32_t pos;
         const uint32_t len = next_token(nowPos32, &pos);
         const uint32_t posState = nowPos32 & pbMask;
@@ -1653,6 +1712,152 @@ struct LzmaEncT {
     o.dest_len = overflow ? dst_cap : outPos;
     return o;
   }
+
+  // One call of an encoder session (fast path only): encode()'s loop, resumed
+  // from and saved to the record S (LzmaEncGpuSession, include/lzma_gpu.h; a
+  // template parameter so that this header needs no other).  src[0, src_len) is
+  // the stream so far; the bytes of the earlier calls are still there, at the
+  // same offsets, though not necessarily at the same address.  The slice
+  // (lzmaenc_layout(q, src_cap)) has been through lzmaenc_init_slice before
+  // the first call that finds work and is untouched since.  `hold` is
+  // kSessionHold everywhere but in the test that shortens it.
+  //
+  // Why the bytes do not depend on the piece sizes.  The one-shot encoder looks
+  // at the bytes left in three places: lenLimit = min(fb, left) in the finder,
+  // numAvail (clamped to kMatchLenMax where it is used, read_match_distances
+  // and get_optimum_fast; compared with 2 there as well), and `left < 4` in the
+  // skip.  A token that starts at p steps the finder at positions p .. p + 272
+  // only: its own read at p (made during the token before when
+  // additionalOffset == 1), one read ahead at p + 1, then a skip to the last
+  // byte of a match of at most kMatchLenMax.  With src_len - p >= 2 *
+  // kMatchLenMax at the token's start, `left` is at least 274 at every one of
+  // them: lenLimit is fb, numAvail is above its clamp, the skip hashes.  So each
+  // of the three values decides what the full length would; the token and the
+  // finder's tables are the one-shot encoder's, by induction over the tokens.
+  // The check is made before every token, also one whose matches were read
+  // ahead (additionalOffset == 1): a run of literals with read-ahead never
+  // returns to additionalOffset == 0, and would otherwise outrun the input.
+  template <class S>
+  LZENC_FN void session_call(S& s, const uint32_t* crc_, uint32_t hold) {
+    static_assert(!kNormal, "sessions are fast-path only");
+    if (s.finished) return;  // done or dead: nothing changes
+    const Params q = session_params(s);
+    const int32_t bad = session_check(s);
+    if (bad != kOk) {
+      s.res = bad;
+      s.status = kSessionFinished;
+      s.finished = 1;
+      return;
+    }
+    if (!s.finish && s.src_len - s.in_pos < hold) {
+      s.status = kSessionNeedsInput;
+      return;
+    }
+    const Layout l = lzmaenc_layout(q, s.src_cap);
+    uint8_t* slice = static_cast<uint8_t*>(s.ws);
+    src = s.src;
+    dst = s.dst;
+    probs = reinterpret_cast<uint16_t*>(slice + l.probs);
+    matches = reinterpret_cast<uint32_t*>(slice + l.matches);
+    hash = reinterpret_cast<uint32_t*>(slice + l.hash);
+    son = reinterpret_cast<uint32_t*>(slice + l.son);
+    crc = crc_;
+    src_len = uint32_t(s.src_len);
+    dst_cap = s.dst_cap;
+    lc = q.lc;
+    lpMask = (1u << q.lp) - 1;
+    pbMask = (1u << q.pb) - 1;
+    numFastBytes = q.fb;
+    cutValue = q.mc;
+    writeEndMark = q.write_end_mark;
+    hashMask = hash_mask(q.dict_size);
+    cyclicBufferSize = q.dict_size + 1;
+    if (s.needs_init) {  // MatchFinder_Init and LzmaEnc_Init, as in encode()
+      off = cyclicBufferPos = 0;
+      state = 0;
+      rep0 = rep1 = rep2 = rep3 = 0;
+      low = 0;
+      range = 0xFFFFFFFFu;
+      cacheSize = 1;
+      cache = 0;
+      outPos = 0;
+      additionalOffset = 0;
+      longestMatchLength = numPairs = numAvail = 0;
+      nowPos64 = 0;
+      overflow = 0;
+    } else {
+      off = s.off;
+      cyclicBufferPos = s.cyclic_pos;
+      state = s.state;
+      rep0 = s.reps[0];
+      rep1 = s.reps[1];
+      rep2 = s.reps[2];
+      rep3 = s.reps[3];
+      low = s.low;
+      range = s.range;
+      cacheSize = s.cache_size;
+      cache = s.cache;
+      outPos = s.out_total;
+      additionalOffset = s.additional_offset;
+      longestMatchLength = s.longest_match_length;
+      numPairs = s.num_pairs;
+      numAvail = s.num_avail;
+      nowPos64 = uint32_t(s.in_pos);
+      overflow = s.overflow;
+      // a record that is not one this function saved steers no access: what
+      // indexes memory is checked against what it is derived from
+      uint32_t maxRep = rep0 > rep1 ? rep0 : rep1;
+      if (rep2 > maxRep) maxRep = rep2;
+      if (rep3 > maxRep) maxRep = rep3;
+      if (additionalOffset > 1 || off != nowPos64 + additionalOffset || off > src_len ||
+          cyclicBufferPos != off % cyclicBufferSize || state >= kNumStates ||
+          maxRep >= nowPos64 || numPairs > kMatchesWords || (numPairs & 1)) {
+        s.res = kErrParam;
+        s.status = kSessionFinished;
+        s.finished = 1;
+        return;
+      }
+    }
+    finished = 0;
+    const uint32_t finish = s.finish ? 1u : 0u;
+    const uint32_t startPos = nowPos64;
+    int32_t status = kSessionNeedsInput;
+    for (;;) {
+      code_block<false, true>(finish, hold);
+      if (finished) break;
+      if (!finish && src_len - nowPos64 < hold) break;
+      if (s.in_budget != 0 && nowPos64 - startPos >= s.in_budget) {
+        status = kSessionBudget;
+        break;
+      }
+    }
+    // a write that did not fit ends the session now; the one-shot encoder goes
+    // on to its next CheckErrors, with nothing more reaching dst
+    if (overflow) finished = 1;
+    s.needs_init = 0;
+    s.off = off;
+    s.cyclic_pos = cyclicBufferPos;
+    s.state = state;
+    s.reps[0] = rep0;
+    s.reps[1] = rep1;
+    s.reps[2] = rep2;
+    s.reps[3] = rep3;
+    s.low = low;
+    s.range = range;
+    s.cache_size = cacheSize;
+    s.cache = cache;
+    s.out_total = outPos;
+    s.additional_offset = additionalOffset;
+    s.longest_match_length = longestMatchLength;
+    s.num_pairs = numPairs;
+    s.num_avail = numAvail;
+    s.overflow = overflow;
+    s.finished = finished;
+    s.in_pos = nowPos64;
+    s.out_pos = overflow ? dst_cap : outPos;
+    s.res = overflow ? kErrOutputEof : kOk;
+    s.status = finished ? kSessionFinished : status;
+  }
 };
 using LzmaEnc = LzmaEncT<false>;
 using LzmaEncNormal = LzmaEncT<true>;
@@ -1665,6 +1870,30 @@ LZENC_FN void lzmaenc_init_slice(uint8_t* slice, const Layout& l, uint64_t first
   for (uint64_t i = first; i < l.prob_cells; i += step) probs[i] = uint16_t(kProbInit);
   uint32_t* hash = reinterpret_cast<uint32_t*>(slice + l.hash);
   for (uint64_t i = first; i < l.hash_words; i += step) hash[i] = 0;
+}
+
+// A fresh session record over the caller's buffers (host side): q has passed
+// params_from_props.  Every field is written; the encoder's own are zero until
+// the first call with work resets them (needs_init).
+template <class S>
+LZENC_HD void session_bind(S* s, const Params& q, const uint8_t* src, uint64_t src_cap,
+                           uint8_t* dst, uint64_t dst_cap, void* ws) {
+  S z = S();
+  z.src = src;
+  z.dst = dst;
+  z.ws = ws;
+  z.src_cap = src_cap;
+  z.dst_cap = dst_cap;
+  z.dict_size = q.dict_size;
+  z.lc = q.lc;
+  z.lp = q.lp;
+  z.pb = q.pb;
+  z.fb = q.fb;
+  z.mc = q.mc;
+  z.write_end_mark = q.write_end_mark;
+  z.status = kSessionNeedsInput;
+  z.needs_init = 1;
+  *s = z;
 }
 
 }  // namespace lzenc

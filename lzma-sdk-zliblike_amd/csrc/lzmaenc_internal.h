@@ -79,6 +79,20 @@ uint32_t lzmaenc_allowed_modes();
 // "<what>: props field <field> ..." as the last error of a refused props call
 void lzmaenc_set_unsupported_error(const char* field);
 
+// Encoder sessions (lzmaenc_session_kernels.hip, lzmaenc_session_capi.hip).
+// A round's scratch, in 32-bit words: the header (the two counters, padded to
+// 16 bytes), the work list (n indices), the init list (n indices).
+constexpr uint32_t kLzmaEncSessionWorkCount = 0, kLzmaEncSessionInitCount = 1;
+constexpr uint32_t kLzmaEncSessionHeaderWords = 4;
+// The list pass alone (lzmaenc_session_bench.py times it separately): clears
+// the counters, then compacts.
+extern "C" int lzmaencgpu_session_launch_list(const LzmaEncGpuSession* d_sessions, uint32_t n,
+                                              uint32_t* d_scratch, hipStream_t stream);
+// One round on `stream`: list pass, init over the init list, encode over the
+// work list (lanes 16, 32, 64, or 0 for kLzmaEncLanesDefault).  0 on success.
+extern "C" int lzmaencgpu_session_launch(LzmaEncGpuSession* d_sessions, uint32_t n,
+                                         uint32_t* d_scratch, uint32_t lanes, hipStream_t stream);
+
 // The normal-mode encode kernel alone (lzmaenc_normal_kernels.hip); lanes 16, 32 or 64.
 extern "C" int lzmaencgpu_launch_normal(const LzmaEncGpuStreamDesc* d_descs,
                                         const uint32_t* d_order, uint32_t n, const uint8_t* d_src,

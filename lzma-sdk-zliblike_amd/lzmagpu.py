@@ -10,7 +10,9 @@ There is no fallback: if lib/liblzmagpu.so is missing this module raises at
 import time, and on a machine without a HIP device every decode and encode
 returns SZ_ERROR_FAIL (``LzmaGpu_LastError`` says why).  Encoding (the
 reference's fast path, levels 0..4): ``encode_batch``, ``LzmaEncode``,
-``LzmaCompress`` and the ``LzmaEncGpu_*`` batch calls; LZMA2 and xz writing over
+``LzmaCompress`` and the ``LzmaEncGpu_*`` batch calls; sessions that take their
+streams in pieces: ``LzmaEncSessions``, ``enc_session_*`` and the ``LzmaEnc_*``
+handle drop-ins; LZMA2 and xz writing over
 them: ``lzma2_encode_batch``, ``lzma2_compress``, ``xz_compress`` and the
 ``Lzma2Enc_*`` drop-ins.
 """
@@ -265,6 +267,27 @@ class EncResult(ctypes.Structure):
     _fields_ = [("res", ctypes.c_int32), ("_pad", ctypes.c_uint32), ("dest_len", ctypes.c_uint64)]
 
 
+class EncSession(ctypes.Structure):
+    """LzmaEncGpuSession (include/lzma_gpu.h, 200 bytes): a device-resident
+    fast-mode encoder fed in pieces."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("ws", ctypes.c_void_p),
+                ("src_cap", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64),
+                ("src_len", ctypes.c_uint64), ("in_budget", ctypes.c_uint64),
+                ("in_pos", ctypes.c_uint64), ("out_pos", ctypes.c_uint64),
+                ("dict_size", ctypes.c_uint32), ("lc", ctypes.c_uint32), ("lp", ctypes.c_uint32),
+                ("pb", ctypes.c_uint32), ("fb", ctypes.c_uint32), ("mc", ctypes.c_uint32),
+                ("write_end_mark", ctypes.c_uint32), ("finish", ctypes.c_uint32),
+                ("res", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("needs_init", ctypes.c_uint32), ("finished", ctypes.c_uint32),
+                ("overflow", ctypes.c_uint32), ("off", ctypes.c_uint32),
+                ("cyclic_pos", ctypes.c_uint32), ("longest_match_length", ctypes.c_uint32),
+                ("num_pairs", ctypes.c_uint32), ("num_avail", ctypes.c_uint32),
+                ("additional_offset", ctypes.c_uint32), ("reps", ctypes.c_uint32 * 4),
+                ("state", ctypes.c_uint32), ("range", ctypes.c_uint32), ("cache", ctypes.c_uint32),
+                ("cache_size", ctypes.c_uint32), ("_pad", ctypes.c_uint32),
+                ("low", ctypes.c_uint64), ("out_total", ctypes.c_uint64)]
+
+
 class SzFolder(ctypes.Structure):
     """LzmaGpu7zFolder (include/lzma_gpu.h): one folder of an opened 7z archive."""
     _fields_ = [("pack_off", ctypes.c_uint64), ("pack_size", ctypes.c_uint64),
@@ -488,6 +511,24 @@ _sig = {
     "LzmaGpu_Lzma2EncodeHost": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t,
                                                ctypes.POINTER(CLzma2EncProps),
                                                ctypes.POINTER(ctypes.c_ubyte)]),
+    "LzmaEncGpu_SessionWorkspaceBytes": (ctypes.c_uint64, [ctypes.POINTER(CLzmaEncProps),
+                                                           ctypes.c_uint64]),
+    "LzmaEncGpu_SessionInit": (ctypes.c_int, [ctypes.POINTER(EncSession),
+                                              ctypes.POINTER(CLzmaEncProps), ctypes.c_int, _P,
+                                              ctypes.c_uint64, _P, ctypes.c_uint64, _P, _P]),
+    "LzmaEncGpu_SessionScratchBytes": (ctypes.c_size_t, [ctypes.c_size_t]),
+    "LzmaEncGpu_SessionEncodeBatch": (ctypes.c_int, [_P, ctypes.c_size_t, _P, ctypes.c_uint, _P]),
+    "LzmaEncGpu_SessionListPass": (ctypes.c_int, [_P, ctypes.c_size_t, _P, _P]),
+    "LzmaEnc_Create": (ctypes.c_void_p, [ctypes.POINTER(ISzAlloc)]),
+    "LzmaEnc_Destroy": (None, [ctypes.c_void_p, ctypes.POINTER(ISzAlloc),
+                               ctypes.POINTER(ISzAlloc)]),
+    "LzmaEnc_SetProps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CLzmaEncProps)]),
+    "LzmaEnc_WriteProperties": (ctypes.c_int, [ctypes.c_void_p, _P, _sp]),
+    "LzmaEnc_Encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ISeqOutStream),
+                                      ctypes.POINTER(ISeqInStream),
+                                      ctypes.POINTER(ICompressProgress), _P, _P]),
+    "LzmaEnc_MemEncode": (ctypes.c_int, [ctypes.c_void_p, _P, _sp, _P, ctypes.c_size_t,
+                                         ctypes.c_int, _P, _P, _P]),
     "Lzma2Enc_Create": (ctypes.c_void_p, [ctypes.POINTER(ISzAlloc), ctypes.POINTER(ISzAlloc)]),
     "Lzma2Enc_Destroy": (None, [ctypes.c_void_p]),
     "Lzma2Enc_SetProps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CLzma2EncProps)]),
@@ -1406,6 +1447,185 @@ def LzmaCompress(src, dest_cap, level=5, dict_size=0, lc=-1, lp=-1, pb=-1, fb=-1
                             dict_size, lc, lp, pb, fb, num_threads)
     ok = res in (SZ_OK, SZ_ERROR_OUTPUT_EOF)
     return res, dl.value, pe.raw[:5], d.raw[:dl.value] if ok else b""
+
+
+# ---------------------------------------------------------------- LZMA encoder sessions
+
+ENC_SESSION_HOLD = 546
+ENC_SESSION_NEEDS_INPUT, ENC_SESSION_FINISHED, ENC_SESSION_BUDGET = 0, 1, 2
+SZ_ERROR_READ, SZ_ERROR_WRITE, SZ_ERROR_PROGRESS = 8, 9, 10
+
+
+def enc_session_workspace_bytes(props, src_cap):
+    """LzmaEncGpu_SessionWorkspaceBytes."""
+    return _lib.LzmaEncGpu_SessionWorkspaceBytes(ctypes.byref(props), src_cap)
+
+
+def enc_session_init(s, props, d_src, src_cap, d_dst, dst_cap, d_ws, end_mark=False):
+    """LzmaEncGpu_SessionInit into the EncSession s (device pointers as ints):
+    (res, props5)."""
+    props5 = ctypes.create_string_buffer(5)
+    r = _lib.LzmaEncGpu_SessionInit(ctypes.byref(s), ctypes.byref(props), 1 if end_mark else 0,
+                                    d_src or None, src_cap, d_dst or None, dst_cap, d_ws or None,
+                                    props5)
+    return r, props5.raw
+
+
+def enc_session_scratch_bytes(n):
+    return _lib.LzmaEncGpu_SessionScratchBytes(n)
+
+
+def enc_session_encode_batch(d_sessions, n, d_scratch, lanes=0, stream=0):
+    """LzmaEncGpu_SessionEncodeBatch over a device array of n EncSessions."""
+    return _lib.LzmaEncGpu_SessionEncodeBatch(d_sessions, n, d_scratch, lanes, stream or None)
+
+
+def enc_session_list_pass(d_sessions, n, d_scratch, stream=0):
+    """The round's list pass alone (lzmaenc_session_bench.py)."""
+    return _lib.LzmaEncGpu_SessionListPass(d_sessions, n, d_scratch, stream or None)
+
+
+class LzmaEncSessions:
+    """n encoder sessions on torch device tensors: one
+    source, destination and workspace slab each, cut evenly; the records live
+    on the device and are mirrored here.
+
+        s = LzmaEncSessions(n, src_cap, dst_cap, level=1)   # or props=[...] per session
+        s.append(i, piece)        # any number of sessions, any piece sizes
+        s.round(finish=[...])     # one LzmaEncGpu_SessionEncodeBatch
+        s.drain(i)                # the bytes of session i that are new
+
+    After round(), s.rec[i] holds res / status / in_pos / out_pos."""
+
+    def __init__(self, n, src_cap, dst_cap, end_mark=False, device="cuda", props=None,
+                 dst_caps=None, poison=None, **kw):
+        """props: one CLzmaEncProps or a list of n (default: enc_props(**kw));
+        end_mark: one flag or a list of n; dst_caps: per-session capacities at
+        most dst_cap (the slot size); poison: a byte the destination and the
+        workspace are filled with first."""
+        import torch
+        self.torch, self.n, self.src_cap, self.dst_cap = torch, n, src_cap, dst_cap
+        plist = list(props) if isinstance(props, (list, tuple)) else [props or enc_props(**kw)] * n
+        marks = list(end_mark) if isinstance(end_mark, (list, tuple)) else [end_mark] * n
+        caps = list(dst_caps) if dst_caps is not None else [dst_cap] * n
+        self.ws_bytes = [enc_session_workspace_bytes(p, src_cap) for p in plist]
+        if any(b == 0 for b in self.ws_bytes):
+            raise ValueError("props or src_cap refused: " + last_error())
+        self.ws_off = [sum(self.ws_bytes[:i]) for i in range(n)]
+
+        def slab(nbytes, fill=None):
+            if fill is None:
+                return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+            return torch.full((max(nbytes, 16),), fill, dtype=torch.uint8, device=device)
+        self.src, self.dst = slab(n * src_cap), slab(n * dst_cap, poison)
+        self.ws = slab(sum(self.ws_bytes), poison)
+        self.scratch = slab(enc_session_scratch_bytes(n))
+        self.rec = (EncSession * max(n, 1))()
+        self.props5 = [b""] * n
+        for i in range(n):
+            r, self.props5[i] = enc_session_init(
+                self.rec[i], plist[i], self.src.data_ptr() + i * src_cap, src_cap,
+                self.dst.data_ptr() + i * dst_cap, caps[i], self.ws.data_ptr() + self.ws_off[i],
+                marks[i])
+            if r != SZ_OK:
+                raise ValueError("LzmaEncGpu_SessionInit: %d %s" % (r, last_error()))
+        self.d_rec = slab(ctypes.sizeof(self.rec))
+        self.supplied = [0] * n
+        self.drained = [0] * n
+        self._upload()
+
+    def _host(self):
+        return self.torch.frombuffer(self.rec, dtype=self.torch.uint8)
+
+    def _upload(self):
+        self.d_rec[:ctypes.sizeof(self.rec)].copy_(self._host())
+
+    def append(self, i, piece):
+        """Appends piece (bytes) to session i's source on the device."""
+        if not piece:
+            return
+        at = self.supplied[i]
+        assert at + len(piece) <= self.src_cap
+        t = self.torch.frombuffer(bytearray(piece), dtype=self.torch.uint8)
+        self.src[i * self.src_cap + at:i * self.src_cap + at + len(piece)].copy_(t)
+        self.supplied[i] = at + len(piece)
+
+    def round(self, finish=(), in_budget=0, lanes=0, sync=True):
+        """One round over all n sessions; finish: indices whose stream is
+        complete.  Returns LzmaEncGpu_SessionEncodeBatch's result."""
+        fin = set(finish)
+        for i in range(self.n):
+            self.rec[i].src_len = self.supplied[i]
+            self.rec[i].finish = 1 if i in fin else 0
+            self.rec[i].in_budget = in_budget
+        self._upload()
+        r = enc_session_encode_batch(self.d_rec.data_ptr(), self.n, self.scratch.data_ptr(), lanes,
+                                     self.torch.cuda.current_stream().cuda_stream)
+        if sync:
+            self.download()
+        return r
+
+    def download(self):
+        self._host().copy_(self.d_rec[:ctypes.sizeof(self.rec)])
+
+    def worked(self):
+        """Sessions the last round listed as having work (scratch word 0)."""
+        return int(self.scratch[:4].view(self.torch.int32)[0])
+
+    def drain(self, i):
+        """dst[drained, out_pos) of session i: the bytes not yet taken."""
+        upto = min(self.rec[i].out_pos, self.rec[i].dst_cap)
+        lo = self.drained[i]
+        self.drained[i] = upto
+        return bytes(self.dst[i * self.dst_cap + lo:i * self.dst_cap + upto].cpu().numpy())
+
+
+def LzmaEnc_Encode(read, write, props, progress=None):
+    """The handle drop-ins end to end: Create, SetProps, WriteProperties, Encode
+    over Python callables -- read(n) -> bytes (b"" at the end), write(b) -> count
+    taken, progress(in, out) -> 0 to go on -- and Destroy.  (res, props5)."""
+    h = _lib.LzmaEnc_Create(ctypes.byref(g_alloc))
+    try:
+        r = _lib.LzmaEnc_SetProps(h, ctypes.byref(props))
+        if r != SZ_OK:
+            return r, b""
+        p5 = ctypes.create_string_buffer(5)
+        ps = ctypes.c_size_t(5)
+        r = _lib.LzmaEnc_WriteProperties(h, p5, ctypes.byref(ps))
+        if r != SZ_OK:
+            return r, b""
+
+        def _read(_p, buf, size):
+            b = read(size[0])
+            ctypes.memmove(buf, b, len(b))
+            size[0] = len(b)
+            return SZ_OK
+
+        def _write(_p, buf, size):
+            return write(ctypes.string_at(buf, size))
+        ins, outs = ISeqInStream(SeqRead(_read)), ISeqOutStream(SeqWrite(_write))
+        prog = ICompressProgress(ProgressFn(lambda _p, a, b: progress(a, b))) if progress else None
+        r = _lib.LzmaEnc_Encode(h, ctypes.byref(outs), ctypes.byref(ins),
+                                ctypes.byref(prog) if prog else None, None, None)
+        return r, p5.raw
+    finally:
+        _lib.LzmaEnc_Destroy(h, ctypes.byref(g_alloc), ctypes.byref(g_alloc))
+
+
+def LzmaEnc_MemEncode(src, props, dest_cap, end_mark=False):
+    """LzmaEnc_Create / SetProps / MemEncode / Destroy: (res, packed)."""
+    h = _lib.LzmaEnc_Create(ctypes.byref(g_alloc))
+    try:
+        r = _lib.LzmaEnc_SetProps(h, ctypes.byref(props))
+        if r != SZ_OK:
+            return r, b""
+        d = ctypes.create_string_buffer(max(dest_cap, 1))
+        dl = ctypes.c_size_t(dest_cap)
+        r = _lib.LzmaEnc_MemEncode(h, d, ctypes.byref(dl), _buf(src), len(src),
+                                   1 if end_mark else 0, None, None, None)
+        return r, d.raw[:dl.value] if r in (SZ_OK, SZ_ERROR_OUTPUT_EOF) else b""
+    finally:
+        _lib.LzmaEnc_Destroy(h, ctypes.byref(g_alloc), ctypes.byref(g_alloc))
 
 
 # ---------------------------------------------------------------- LZMA2 and xz writing
