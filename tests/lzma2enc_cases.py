@@ -2,7 +2,7 @@
 (test_lzma2enc_emu.py, test_lzma2enc_gpu.py, test_lzma2enc_abi.py) and by
 tests/golden/make_golden_lzma2enc.py.
 
-A case is a list of (kind, seed, n) segments for native.gen, concatenated, plus
+A case is a list of (kind, seed, n) segments for gen() below, concatenated, plus
 the props a caller sets (level, dict, lc, lp, pb).  Inputs are generated, never
 stored.  The expected bytes are the reference's single-threaded Lzma2Enc_Encode
 of the case as one block (native.ref()'s ref_lzma2_encode) -- live where
@@ -18,6 +18,7 @@ import random
 import struct
 import subprocess
 
+import lzmaenc_cases
 import native
 
 GOLDEN = os.path.join(native.ROOT, "tests", "golden", "lzma2enc_cases.json")
@@ -72,8 +73,16 @@ def data_of(c):
     if k not in _data:
         if len(_data) > 64:
             _data.clear()
-        _data[k] = b"".join(native.gen(kind, seed, n) for kind, seed, n in c["segs"])
+        _data[k] = b"".join(gen(kind, seed, n) for kind, seed, n in c["segs"])
     return _data[k]
+
+
+def gen(kind, seed, n):
+    """native.gen's three kinds; "copy" and "far:GAP" are lzmaenc_cases.gen's, so
+    that an LZMA2 block and an LZMA stream of the same name see the same bytes."""
+    if kind in ("text", "random", "runs"):
+        return native.gen(kind, seed, n)
+    return lzmaenc_cases.gen(kind, seed, n)
 
 
 def block_bound(n):

@@ -32,11 +32,25 @@ _WORDS = [w.encode() for w in (
     "use may water long little very after words called just where most know").split()]
 
 
-def gen(kind, seed, n):
-    """n bytes of one of the data kinds, from incompressible to one repeated byte."""
+def far(seed, n, gap):
+    """A 1 KiB block that returns after `gap` random bytes (a match at distance
+    1024 + gap) and again, in part, 512 bytes later; random bytes up to n.  The
+    filler is incompressible: the only long matches are the far ones."""
     rng = random.Random(seed)
+    b = rng.randbytes(1024)
+    out = b + rng.randbytes(gap) + b + rng.randbytes(512) + b[100:900]
+    return (out + rng.randbytes(max(0, n - len(out))))[:n]
+
+
+def gen(kind, seed, n):
+    """n bytes of one of the data kinds, from incompressible to one repeated byte.
+    "far:GAP" is far(seed, n, GAP): the name carries the gap, so that a case
+    stays (kind, seed, n) here and in the LZMA2 segment lists."""
     if n == 0:
         return b""
+    if kind.startswith("far:"):
+        return far(seed, n, int(kind[4:]))
+    rng = random.Random(seed)
     if kind == "random":
         return rng.randbytes(n)
     if kind == "byte":
