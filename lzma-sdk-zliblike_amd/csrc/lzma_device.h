@@ -282,6 +282,11 @@ enum : uint32_t {
   W_MB,      // the matched byte at rep0, loaded at match end
   W_INPUT,   // input blocks (reader refills)
   W_PREV,    // the previous byte at a pass's start, the look-ahead probe
+  // (round 8; counters 36 and 37 of LzmaGpu_ProfileRead)
+  W_FETCH,   // GlobalReaderQ: from a block fetch's issue to the end of a forced
+             // wait behind it -- the wait the default build's copy of the
+             // loaded block takes in the same place
+  W_WALK,    // the wait at the head of the plain literal walk
   W_N
 };
 __device__ __forceinline__ void lz_wait_into(uint64_t& acc) {
@@ -633,6 +638,7 @@ struct GlobalReaderQ {
   uint32_t taken;  // bytes moved into win since init (consumed = taken - nb)
 #if LZGPU_PROF && !defined(LZGPU_HOST_EMU)
   uint64_t prof = 0;  // (refills are not timed separately in this reader)
+  uint64_t prof_fetch = 0;  // LZGPU_PROF=3: W_FETCH
 #endif
 
   __device__ __forceinline__ void fetch() {
@@ -656,7 +662,14 @@ struct GlobalReaderQ {
       blo = uint64_t(nx.x) | (uint64_t(nx.y) << 32);
       bhi = uint64_t(nx.z) | (uint64_t(nx.w) << 32);
       bw = 4;
+#if LZGPU_PROF == 3 && !defined(LZGPU_HOST_EMU)
+      const uint64_t t0 = __builtin_amdgcn_s_memtime();
       fetch();
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      prof_fetch += __builtin_amdgcn_s_memtime() - t0;
+#else
+      fetch();
+#endif
     }
   }
   __device__ __forceinline__ void init(const gbyte* p, uint64_t avail) {
@@ -707,8 +720,165 @@ struct GlobalReaderQ {
     }
   }
 };
+// a value the compiler must not relate to the others (keeps a select of two
+// registers a select)
+template <class T>
+__host__ __device__ __forceinline__ void lz_opaque(T& x) {
+#ifndef LZGPU_HOST_EMU
+  asm("" : "+v"(x));
+#else
+  (void)x;
+#endif
+}
+// Input reader of the throughput placement (round 8):
+//   0: GlobalReaderQ, as in the cooperative kernels; 1: GlobalReaderP
+#ifndef LZGPU_READER
+#define LZGPU_READER 1
+#endif
+// (a, b) = (x, y) as two register moves the compiler cannot fold into a use
+// of x and y themselves, and a point no memory access is moved across: x and y
+// are dead below it (host emulation: plain assignments)
+__host__ __device__ __forceinline__ void lz_move2(uint64_t& a, uint64_t& b, uint64_t x,
+                                                  uint64_t y) {
+#ifndef LZGPU_HOST_EMU
+  asm volatile("v_mov_b64 %0, %2\n\tv_mov_b64 %1, %3"
+               : "=&v"(a), "=&v"(b)
+               : "v"(x), "v"(y)
+               : "memory");
+#else
+  a = x;
+  b = y;
+#endif
+}
+// GlobalReaderQ's contract with a prefetch that stays in flight.  In the
+// throughput kernel GlobalReaderQ's fetch() is scheduled above the last read
+// of the block it replaces, so the load gets a tuple of its own, is waited for
+// at once (vmcnt(0): behind every store in flight too) and copied to nx -- a
+// synchronous round trip on the decision chain at every block.  Here the
+// promoted block's words are pinned in blo:bhi before the next fetch is issued
+// (lz_move2), so the load lands in nx's own registers and the first wait that
+// covers it is the promotion 16 input bytes later.
+struct GlobalReaderP {
+#ifdef LZGPU_HOST_EMU
+  struct u32x4 { uint32_t x, y, z, w; };
+#else
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#endif
+  const gu32* wp;  // next 16-byte block to prefetch (as words)
+  uint32_t left;   // blocks with a valid byte still to prefetch
+  uint32_t nb;     // valid bytes in win (0..8)
+  uint32_t bw;     // words left in blo:bhi (1..4)
+  uint64_t win;
+  uint64_t blo, bhi;
+  u32x4 nx;        // the block in flight, in the load's own registers
+  uint32_t taken;  // bytes moved into win since init (consumed = taken - nb)
+#if LZGPU_PROF && !defined(LZGPU_HOST_EMU)
+  uint64_t prof = 0;        // LZGPU_PROF=3: the waits at promotions (W_INPUT)
+  uint64_t prof_fetch = 0;  // (no wait behind a fetch in this reader)
+#endif
+
+  __device__ __forceinline__ void fetch() {
+    const gu32* a = left ? wp : (const gu32*)g_lz_zero_word;
+#ifdef LZGPU_HOST_EMU
+    nx = u32x4{a[0], a[1], a[2], a[3]};
+#else
+    nx = *(const __attribute__((address_space(1))) u32x4*)a;
+#endif
+    wp += left ? 4 : 0;
+    left -= left ? 1u : 0u;
+  }
+  // the prefetched block becomes the current one, then the next is requested
+  __device__ __forceinline__ void promote() {
+#if LZGPU_PROF == 3 && !defined(LZGPU_HOST_EMU)
+    lz_wait_into(prof);
+#endif
+    // nx's last read is here, the load below: nothing of nx is live across it
+    lz_move2(blo, bhi, uint64_t(nx.x) | (uint64_t(nx.y) << 32),
+             uint64_t(nx.z) | (uint64_t(nx.w) << 32));
+    bw = 4;
+    fetch();
+  }
+  __device__ __forceinline__ void pop_word() {
+    blo = (blo >> 32) | (bhi << 32);
+    bhi >>= 32;
+    if (--bw == 0) promote();
+  }
+  // The checkpoint between the halves of a literal's tree walk: a promotion
+  // there leaves its fetch to fetch_pending(), which the literal calls behind
+  // the walk, before any other use of the reader.  The walk exists in two code
+  // regions (plain, fused); a load issued inside them gives nx one definition
+  // per region, and the copies that merge them at the join wait for the load.
+  static constexpr uint32_t kFetchDue = 0x100u;
+  __device__ __forceinline__ void topup_mid() {
+    if (nb <= 4) {
+      win |= uint64_t(uint32_t(blo)) << (8 * nb);
+      nb += 4;
+      taken += 4;
+      blo = (blo >> 32) | (bhi << 32);
+      bhi >>= 32;
+      if (--bw == 0) {
+#if LZGPU_PROF == 3 && !defined(LZGPU_HOST_EMU)
+        lz_wait_into(prof);
+#endif
+        blo = uint64_t(nx.x) | (uint64_t(nx.y) << 32);
+        bhi = uint64_t(nx.z) | (uint64_t(nx.w) << 32);
+        bw = 4 | kFetchDue;
+      }
+    }
+  }
+  __device__ __forceinline__ void fetch_pending() {
+    if (bw > 4) {
+      bw = 4;
+      fetch();  // (nx's last read was topup_mid()'s)
+    }
+  }
+  __device__ __forceinline__ void init(const gbyte* p, uint64_t avail) {
+    const uintptr_t a = (uintptr_t)p;
+    const uintptr_t a0 = a & ~uintptr_t(15);
+    const uint64_t blocks = avail ? (((a + avail + 15) & ~uintptr_t(15)) - a0) >> 4 : 0;
+    wp = (const gu32*)a0;
+    left = blocks > 0xFFFFFFF0ull ? 0xFFFFFFF0u : uint32_t(blocks);
+    fetch();
+    promote();
+    // skip the words of the first block before p, then the bytes of p's word
+    for (uint32_t w = uint32_t(a & 15) >> 2; w != 0; --w) pop_word();
+    const uint32_t sk = uint32_t(a & 3);
+    win = uint64_t(uint32_t(blo)) >> (8 * sk);
+    nb = avail ? 4 - sk : 0;
+    pop_word();
+    taken = nb;
+  }
+  __device__ __forceinline__ uint32_t used() const { return taken - nb; }
+  __device__ __forceinline__ void topup() {
+    if (nb <= 4) {
+      win |= uint64_t(uint32_t(blo)) << (8 * nb);
+      nb += 4;
+      taken += 4;
+      pop_word();
+    }
+  }
+  __device__ __forceinline__ uint32_t peek() const { return uint32_t(win) & 0xFFu; }
+  __device__ __forceinline__ uint32_t take_u() {
+    const uint32_t b = uint32_t(win) & 0xFFu;
+    win >>= 8;
+    --nb;
+    return b;
+  }
+  __device__ __forceinline__ uint32_t next() {
+    if (nb == 0) topup();
+    return take_u();
+  }
+  __device__ __forceinline__ void advance(bool n) {
+    if (n) {
+      win >>= 8;
+      --nb;
+      if (nb == 0) topup();
+    }
+  }
+};
+// the checkpoint readers (topup / take_u)
 template <class Rd>
-constexpr bool kIsQ = __is_same(Rd, GlobalReaderQ);
+constexpr bool kIsQ = __is_same(Rd, GlobalReaderQ) || __is_same(Rd, GlobalReaderP);
 
 typedef GlobalReader16 PlainReader;
 // Reader of the bulk pass per placement: the checkpoint reader for the
@@ -810,16 +980,6 @@ __host__ __device__ __forceinline__ LS lds_at<LS>(lds_addr_t a) {
 }
 template <class P>
 constexpr lds_addr_t kLdsStep = __is_same(P, LS) ? lds_addr_t(2u * kIlv) : lds_addr_t(2u);
-// a value the compiler must not relate to the others (keeps a select of two
-// registers a select)
-template <class T>
-__host__ __device__ __forceinline__ void lz_opaque(T& x) {
-#ifndef LZGPU_HOST_EMU
-  asm("" : "+v"(x));
-#else
-  (void)x;
-#endif
-}
 template <uint32_t M>
 __host__ __device__ constexpr bool def_on() {
   return LZGPU_WIN_DEFER != 0 && win_on<M>() && (M & kCoopBit) != 0u;
@@ -842,7 +1002,11 @@ struct BulkReaderFor {
   static constexpr uint32_t m = M & ~kIlvBit;
   static constexpr bool q = m == LZGPU_LDS_MASK || m == (LZGPU_LDS_MASK_LAT | kCoopBit) ||
                             m == (LZGPU_LDS_MASK_ALL | kCoopBit);
-  typedef typename std::conditional<q, GlobalReaderQ, PlainReader>::type type;
+  // the throughput placement's own reader (LZGPU_READER)
+  static constexpr bool p = LZGPU_READER != 0 && m == LZGPU_LDS_MASK;
+  typedef typename std::conditional<
+      p, GlobalReaderP,
+      typename std::conditional<q, GlobalReaderQ, PlainReader>::type>::type type;
 };
 
 // Matched-byte prefetch per placement: the byte at rep0 is loaded at match end in
@@ -860,6 +1024,18 @@ __host__ __device__ constexpr bool mb_pf_on() {
 template <class Rd>
 __device__ __forceinline__ void rd_topup(Rd& rd) {
   if constexpr (kIsQ<Rd>) rd.topup();
+}
+// the literal's mid-walk checkpoint and the fetch it may leave behind
+template <class Rd>
+__device__ __forceinline__ void rd_topup_mid(Rd& rd) {
+  if constexpr (__is_same(Rd, GlobalReaderP))
+    rd.topup_mid();
+  else
+    rd_topup(rd);
+}
+template <class Rd>
+__device__ __forceinline__ void rd_fetch_pending(Rd& rd) {
+  if constexpr (__is_same(Rd, GlobalReaderP)) rd.fetch_pending();
 }
 template <class Rd>
 __device__ __forceinline__ uint32_t rd_take_u(Rd& rd) {
@@ -1097,7 +1273,7 @@ struct Rc {
     lds_addr_t a = base + st;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      if (k == 4) rd_topup(*rd);
+      if (k == 4) rd_topup_mid(*rd);
       const uint32_t b = bit_u(lds_at<P>(a));
       a = (a << 1) + (b ? k1 : k0);
     }
@@ -1632,7 +1808,7 @@ __device__ __forceinline__ void lz_literal(Rc<Rd, U, F>& rc, const Tab<M, Lo>& T
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const uint32_t mk = (mb >> (7 - k)) & 1u;
-        if (k == 4) rd_topup(*rc.rd);
+        if (k == 4) rd_topup_mid(*rc.rd);
         const P cell = lds_at<P>(a);
         const uint32_t pl = *cell;
         const uint32_t p = matched ? pk[k] : pl;
@@ -1649,6 +1825,8 @@ __device__ __forceinline__ void lz_literal(Rc<Rd, U, F>& rc, const Tab<M, Lo>& T
       sym = uint32_t((a - base) / stp);
     } else {
       st = (st < 4) ? 0 : st - 3;
+      LZ_WCLS(rc, W_WALK);
+      rc.wstamp();
       sym = rc.tree8_a(lp);
     }
   } else if (lz_br<U>(st < 7)) {
@@ -1658,7 +1836,7 @@ __device__ __forceinline__ void lz_literal(Rc<Rd, U, F>& rc, const Tab<M, Lo>& T
       sym = rc.tree8_a(lp);
     } else {
       const uint32_t m = rc.template tree_u<4>(lp, 1);
-      rd_topup(*rc.rd);
+      rd_topup_mid(*rc.rd);
       sym = rc.template tree_u<4>(lp, m);
     }
   } else {
@@ -1685,7 +1863,7 @@ __device__ __forceinline__ void lz_literal(Rc<Rd, U, F>& rc, const Tab<M, Lo>& T
       for (int k = 0; k < 8; ++k) {
         const uint32_t mk = (mb >> (7 - k)) & 1u;
         uint32_t b;
-        if (k == 4) rd_topup(*rc.rd);
+        if (k == 4) rd_topup_mid(*rc.rd);
         if (matched)
           b = rc.bit_vu(pk[k], lm + ((mk << 8) + sym));
         else
@@ -1707,6 +1885,7 @@ __device__ __forceinline__ void lz_literal(Rc<Rd, U, F>& rc, const Tab<M, Lo>& T
     }
   }
   prev = sym & 0xFFu;
+  rd_fetch_pending(*rc.rd);
   if constexpr (def_on<M>()) {
     win_put(*w, prev);
     if (++w->fl >= kDeferBytes) win_flush(*w, dic, pos + 1);
@@ -2630,6 +2809,7 @@ __device__ __forceinline__ int lz_decode_to_dic(LzStateT<Lo>& s, uint64_t dic_li
 #if LZGPU_PROF && !defined(LZGPU_HOST_EMU)
 #if LZGPU_PROF == 3
       s.wprof[W_INPUT] += rd.prof;
+      if constexpr (kIsQ<typename BulkReaderFor<M>::type>) s.wprof[W_FETCH] += rd.prof_fetch;
 #else
       s.prof[4] += rd.prof;
 #endif
