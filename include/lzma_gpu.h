@@ -227,6 +227,20 @@ void LzmaGpu_CoalesceStats(uint64_t *batches, uint64_t *calls, uint64_t *max_bat
  * *batches = batches timed.  Either pointer may be NULL. */
 #define LZMA_GPU_COALESCE_PHASES 8
 void LzmaGpu_CoalesceTimes(uint64_t *ns, uint64_t *batches, int reset);
+/* Which path the drop-in decode entry points took, counted once per batch,
+ * call or launch since start or the last reset (the paths are picked by size
+ * fields; reading the counts changes nothing): counts[0] one-call batches
+ * staged through pinned memory, [1] staged from the callers' pageable buffers,
+ * [2] whose outputs were downloaded per call instead of in one transfer;
+ * dictionary-interface calls [3] with and [4] without pinned staging, [5]
+ * launched on the wave-cooperative and [6] on the one-lane session kernel, [7]
+ * session launches that carried both kinds; [8] uploads of a whole dictionary
+ * as history; spans written by the host between two calls uploaded in [9] one
+ * piece and [10] two pieces (across the ring end); [11] mirrors evicted by
+ * count or byte budget; [12] pooled device buffers reused.  counts holds
+ * LZMA_GPU_DROPIN_PATHS values and may be NULL (reset only).  Process-wide. */
+#define LZMA_GPU_DROPIN_PATHS 13
+void LzmaGpu_DropinPathStats(uint64_t *counts, int reset);
 
 /* ---------------------------------------------------------------- drop-in LzmaLib.h */
 

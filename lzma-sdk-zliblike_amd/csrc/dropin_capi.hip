@@ -78,6 +78,18 @@ hipError_t xfer(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStr
   return hipMemcpyAsync(dst, src, n, kind, st);
 }
 
+// Which path a batch or call took (LzmaGpu_DropinPathStats): the tiers are
+// picked by size fields, so a test proves from these that the tier it aims at
+// ran.  Counted once per batch, call or launch, never per byte; read-only.
+enum {
+  kPOnePinned, kPOnePageable, kPOnePerCallOut, kPSessPinned, kPSessUnpinned, kPSessCoop,
+  kPSessGlobal, kPSessMixed, kPHistoryUpload, kPSpanOne, kPSpanTwo, kPMirrorEvicted,
+  kPPoolReused, kPPaths
+};
+static_assert(kPPaths == LZMA_GPU_DROPIN_PATHS, "include/lzma_gpu.h");
+std::atomic<uint64_t> g_path[kPPaths];
+void path_hit(int k, uint64_t n = 1) { g_path[k].fetch_add(n, std::memory_order_relaxed); }
+
 // RAII borrow of a pooled call scratch (buffers + its own stream)
 struct ScratchLease {
   CallScratch* s = lzgpu_host::scratch_acquire();
@@ -434,6 +446,8 @@ void run_batch(BatchSet& C, const std::vector<OneCall*>& b) {
   LzmaGpuResult* pin_res = reinterpret_cast<LzmaGpuResult*>(pin_meta + meta_bytes);
   LzmaGpuResult* d_res = reinterpret_cast<LzmaGpuResult*>(d_meta + meta_bytes);
   pc.mark(kTStage);
+  path_hit(pageable ? kPOnePageable : kPOnePinned);
+  if (!bulk_out) path_hit(kPOnePerCallOut);
   bool up_ok = true;
   if (pageable) {
     for (size_t i = 0; i < k && up_ok; ++i)
@@ -634,6 +648,7 @@ void pool_take(DevBuf& b, size_t n, int dev) {
   b.cap = P.v[best].cap;
   P.bytes -= b.cap;
   P.v.erase(P.v.begin() + ptrdiff_t(best));
+  path_hit(kPPoolReused);
 }
 
 struct Mirror {
@@ -736,6 +751,7 @@ std::shared_ptr<Mirror> mirror_get(const CLzmaDec* p, int dev, size_t want,
     bytes -= R.v[victim]->block.cap + R.v[victim]->io.cap;
     dead.push_back(std::move(R.v[victim]));
     R.v.erase(R.v.begin() + ptrdiff_t(victim));
+    path_hit(kPMirrorEvicted);
   }
   return m;
 }
@@ -833,6 +849,9 @@ void run_sess_batch(SessSet& C, const std::vector<SessCall*>& b) {
       glob.push_back(i);
     }
   }
+  path_hit(kPSessCoop, coop.size());
+  path_hit(kPSessGlobal, glob.size());
+  if (!coop.empty() && !glob.empty()) path_hit(kPSessMixed);
   C.h.resize(k);
   size_t j = 0;
   for (size_t i : coop) C.h[j++] = b[i]->q;
@@ -941,9 +960,11 @@ SRes gpu_session_call(CLzmaDec* p, int mode, SizeT dicLimit, const Byte* src, Si
       const SizeT o = op == B ? 0 : op;
       if (np >= o && np - o == dt) {  // the host wrote dic[o, np)
         ok = xfer(d_dic + o, p->dic + o, np - o, hipMemcpyHostToDevice, st) == hipSuccess;
+        path_hit(kPSpanOne);
       } else if (np < o && (B - o) + np == dt) {  // ... across the ring end
         ok = xfer(d_dic + o, p->dic + o, B - o, hipMemcpyHostToDevice, st) == hipSuccess &&
              (np == 0 || xfer(d_dic, p->dic, np, hipMemcpyHostToDevice, st) == hipSuccess);
+        path_hit(np == 0 ? kPSpanOne : kPSpanTwo);
       }
     }
     if (!ok) m->history = false;
@@ -958,6 +979,7 @@ SRes gpu_session_call(CLzmaDec* p, int mode, SizeT dicLimit, const Byte* src, Si
   const size_t dic_room = dicLimit > p->dicPos ? size_t(dicLimit - p->dicPos) : 0;
   const size_t down_max = tab_pad + (mode == 1 ? out_room : dic_room);
   uint8_t* pin = lzgpu_host::scratch_pinned(L.s, std::max(in_pad + tab_pad, down_max));
+  path_hit(pin ? kPSessPinned : kPSessUnpinned);
   // the table: the device copy is current after every successful call
   if (!m->probs_dev) {
     const void* from = p->probs;
@@ -972,9 +994,11 @@ SRes gpu_session_call(CLzmaDec* p, int mode, SizeT dicLimit, const Byte* src, Si
   // write in this call (LzmaDec.c:165-166,176,216,376-408 read dic only when
   // processedPos or checkDicSize is non-zero); uploaded once per mirror
   const bool need_hist = p->processedPos != 0 || p->checkDicSize != 0;
-  if (need_hist && !m->history && p->dicBufSize &&
-      xfer(d_dic, p->dic, p->dicBufSize, hipMemcpyHostToDevice, st) != hipSuccess)
-    return fail("LzmaDec: upload dictionary");
+  if (need_hist && !m->history && p->dicBufSize) {
+    path_hit(kPHistoryUpload);
+    if (xfer(d_dic, p->dic, p->dicBufSize, hipMemcpyHostToDevice, st) != hipSuccess)
+      return fail("LzmaDec: upload dictionary");
+  }
   if (in_size && pin) memcpy(pin, src, in_size);
   if (in_size && xfer(d_io, pin ? pin : src, in_size, hipMemcpyHostToDevice, st) != hipSuccess)
     return fail("LzmaDec: upload src");
@@ -1217,6 +1241,14 @@ void LzmaGpu_CoalesceTimes(uint64_t* ns, uint64_t* batches, int reset) {
     if (ns) ns[k] = reset ? g_tns[k].exchange(0) : g_tns[k].load();
   const uint64_t b = reset ? g_tbatches.exchange(0) : g_tbatches.load();
   if (batches) *batches = b;
+}
+
+void LzmaGpu_DropinPathStats(uint64_t* counts, int reset) {
+  for (int k = 0; k < kPPaths; ++k) {
+    const uint64_t v = reset ? g_path[k].exchange(0, std::memory_order_relaxed)
+                             : g_path[k].load(std::memory_order_relaxed);
+    if (counts) counts[k] = v;
+  }
 }
 
 // ------------------------------------------------------------------ decode entry points

@@ -392,6 +392,7 @@ _sig = {
     "LzmaGpu_DecoderRelease": (None, [ctypes.POINTER(CLzmaDec)]),
     "LzmaGpu_DropinTransferStats": (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "LzmaGpu_CoalesceStats": (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "LzmaGpu_DropinPathStats": (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "LzmaDecode": (ctypes.c_int, [_P, _sp, _P, _sp, ctypes.c_char_p, ctypes.c_uint, ctypes.c_int, _ip, ctypes.POINTER(ISzAlloc)]),
     "LzmaUncompress": (ctypes.c_int, [_P, _sp, _P, _sp, ctypes.c_char_p, ctypes.c_size_t]),
     "Lzma2Dec_AllocateProbs": (ctypes.c_int, [ctypes.POINTER(CLzma2Dec), ctypes.c_ubyte, ctypes.POINTER(ISzAlloc)]),
@@ -590,6 +591,19 @@ def transfer_stats(reset=False):
     _lib.LzmaGpu_DropinTransferStats(ctypes.byref(h), ctypes.byref(d), ctypes.byref(c),
                                      1 if reset else 0)
     return h.value, d.value, c.value
+
+
+DROPIN_PATHS = ("one_pinned", "one_pageable", "one_percall_out", "sess_pinned", "sess_unpinned",
+                "sess_coop", "sess_global", "sess_mixed", "history_upload", "span_one",
+                "span_two", "mirror_evicted", "pool_reused")
+
+
+def path_stats(reset=False):
+    """{path: count} of the drop-in decode entry points (LzmaGpu_DropinPathStats,
+    LZMA_GPU_DROPIN_PATHS values); reset zeroes the counters after reading."""
+    v = (ctypes.c_uint64 * len(DROPIN_PATHS))()
+    _lib.LzmaGpu_DropinPathStats(v, 1 if reset else 0)
+    return dict(zip(DROPIN_PATHS, v))
 
 
 def last_error():

@@ -39,6 +39,10 @@ def test_header_declares_reference_surface():
                      "Lzma2Dec_DecodeToDic", "Lzma2Dec_DecodeToBuf", "Lzma2Decode",
                      "CrcGenerateTable", "CrcUpdate", "CrcCalc"):
         assert ref_name in names
+    # the library's own read-only entry points the tests lean on
+    for own in ("LzmaGpu_DecoderRelease", "LzmaGpu_DropinTransferStats", "LzmaGpu_CoalesceStats",
+                "LzmaGpu_DropinPathStats"):
+        assert own in names
 
 
 def test_library_exports_every_declared_symbol():
@@ -50,6 +54,18 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(LIB)
     for n in header_functions():
         assert hasattr(lib, n)
+
+
+def test_dropin_path_stats_binding_matches_the_header():
+    """lzmagpu.DROPIN_PATHS names as many counters as LZMA_GPU_DROPIN_PATHS; a
+    read with and without reset, and a reset-only call (NULL), work without a
+    device."""
+    import lzmagpu as L
+    n = int(re.search(r"#define\s+LZMA_GPU_DROPIN_PATHS\s+(\d+)", open(HEADER).read()).group(1))
+    assert n == len(L.DROPIN_PATHS) == len(set(L.DROPIN_PATHS))
+    assert set(L.path_stats()) == set(L.DROPIN_PATHS)
+    L.lib.LzmaGpu_DropinPathStats(None, 1)
+    assert not any(L.path_stats(reset=True).values())
 
 
 def test_struct_layouts():
