@@ -47,6 +47,10 @@
  *       Lzma2Enc_WriteProperties replaces Lzma2Enc.h:41 / Lzma2Enc.c:423-432
  *       Lzma2Enc_Encode         replaces Lzma2Enc.h:42-43 / Lzma2Enc.c:434-477
  *                               (differences: at its declaration below)
+ *       Lzma86_Encode           replaces Lzma86.h:71-72 / Lzma86Enc.c:17-108
+ *       Lzma86_GetUnpackSize    replaces Lzma86.h:87 / Lzma86Dec.c:13-22
+ *       Lzma86_Decode           replaces Lzma86.h:107 / Lzma86Dec.c:24-56
+ *                               (differences: at their declarations below)
  *
  *     Encoding covers the reference's fast path (algo 0 with the hash-chain
  *     finder, what levels 0..4 select) and, once switched on with
@@ -1045,7 +1049,8 @@ SRes LzmaEncGpu_DescFromProps(const CLzmaEncProps *props, int writeEndMark,
  * the environment variable LZGPU_ENC_MODES, read once.  With the mask at 0
  * every call behaves as described for the fast path alone.  It governs
  * LzmaEncGpu_DescFromProps, Lzma2EncGpu_DescFromProps, LzmaEncode,
- * LzmaCompress, Lzma2Enc_Encode, LzmaGpu_Lzma2EncodeHost, LzmaGpu_XzEncode and
+ * LzmaCompress, Lzma2Enc_Encode, LzmaGpu_Lzma2EncodeHost, LzmaGpu_XzEncode(Ex),
+ * Lzma86_Encode, the Lzma86Gpu_Encode* calls and
  * the LZMA / LZMA2 / BCJ2 folders of LzmaGpu_7zWritePlan and LzmaGpu_7zWrite.
  * SetModes returns the previous mask (bits above 3 are dropped). */
 unsigned LzmaEncGpu_SetModes(unsigned allowed);
@@ -1343,6 +1348,156 @@ SRes Lzma2Enc_Encode(CLzma2EncHandle p, ISeqOutStream *outStream, ISeqInStream *
  * short, else as LzmaGpu_Lzma2EncodeHost. */
 SRes LzmaGpu_XzEncode(Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
                       const CLzma2EncProps *props, unsigned check_type);
+
+/* One filter of an xz block's chain in front of LZMA2.  id: the ids of
+ * LzmaGpuXzBlock.filter_id (3 delta, 4 x86, 5 PPC, 6 IA64, 7 ARM, 8 ARMT,
+ * 9 SPARC); prop: the delta distance 1..256, or a branch converter's start
+ * offset. */
+typedef struct LzmaGpuXzFilter {   /* 8 bytes */
+  uint32_t id;
+  uint32_t prop;
+} LzmaGpuXzFilter;
+#define LZMA_GPU_XZ_ENC_FILTERS_MAX 3
+
+/* LzmaGpu_XzEncode with a filter chain: every block lists `filters` in order,
+ * then LZMA2.  Per block the chain runs first filter first in the encode
+ * direction over a device copy of the piece, every filter restarting at the
+ * block (x86 state 0, delta state 0, ip = the start offset), one batch per
+ * filter of the chain; the LZMA2 batch encodes the filtered copy and the block
+ * check is computed over the unfiltered source.  In the block header a delta
+ * filter has one property byte (distance - 1), a branch converter none when
+ * its start offset is 0 and four little-endian bytes otherwise.  Checked on
+ * the host before any device work: SZ_ERROR_PARAM for more than
+ * LZMA_GPU_XZ_ENC_FILTERS_MAX filters, a delta distance outside 1..256 or a
+ * start offset that is no multiple of the converter's alignment (the reader's
+ * rule: PPC, ARM and SPARC 4, IA64 16, ARMT 2, x86 1); SZ_ERROR_UNSUPPORTED
+ * for another id.  num_filters == 0 is LzmaGpu_XzEncode, byte for byte. */
+SRes LzmaGpu_XzEncodeEx(Byte *dest, SizeT *destLen, const Byte *src, SizeT srcLen,
+                        const CLzma2EncProps *props, unsigned check_type,
+                        const LzmaGpuXzFilter *filters, unsigned num_filters);
+
+/* ---- Lzma86: LZMA with the x86 filter tried per stream (Lzma86.h) ----------
+ * The header of an Lzma86 stream: byte 0 the filter flag (0 or 1), bytes 1..5
+ * the LZMA props, bytes 6..13 the unpacked size, little-endian; the LZMA
+ * stream follows without an end mark.  Lzma86_Encode with SZ_FILTER_AUTO
+ * encodes the buffer with and without the filter and keeps the smaller result
+ * (Lzma86Enc.c:59-101); in a batch every candidate is one more lane of the
+ * same LzmaEncGpu_EncodeBatch launch, and the choice, the header and the move
+ * of the chosen candidate into the caller's slot run on the device
+ * (csrc/lzma86_device.h). */
+#ifndef __LZMA86_H
+#define LZMA86_SIZE_OFFSET (1 + 5)
+#define LZMA86_HEADER_SIZE (LZMA86_SIZE_OFFSET + 8)
+enum ESzFilterMode { SZ_FILTER_NO, SZ_FILTER_YES, SZ_FILTER_AUTO };
+#endif
+
+/* One stream of an Lzma86 batch (48 bytes): ranges of the caller's packed
+ * buffers (any byte alignment) and Lzma86_Encode's level, dictSize and
+ * filterMode.  Decoding reads the four ranges only. */
+typedef struct Lzma86GpuStreamDesc {
+  uint64_t src_off, src_len;
+  uint64_t dst_off, dst_cap;
+  int32_t level;
+  uint32_t dictSize;
+  int32_t filterMode;   /* SZ_FILTER_* */
+  uint32_t reserved;    /* 0 */
+} Lzma86GpuStreamDesc;
+
+/* Per-stream outcome (24 bytes).  Encoding: Lzma86_Encode's return value and
+ * *destLen, filter = the flag byte written, src_len = the stream's src_len.
+ * Decoding: Lzma86_Decode's return value, *destLen and *srcLen (0 where the
+ * reference leaves it untouched), filter = the flag byte read. */
+typedef struct Lzma86GpuResult {
+  int32_t res;
+  uint32_t filter;
+  uint64_t dest_len;
+  uint64_t src_len;
+} Lzma86GpuResult;
+
+#define LZMA86_GPU_TIMINGS 1u      /* synchronise after every stage and fill stage_ns */
+#define LZMA86_GPU_STAGE_FILTER 0  /* the copies of the sources and the x86 batch */
+#define LZMA86_GPU_STAGE_ENCODE 1  /* the LzmaEncGpu_EncodeBatch launches */
+#define LZMA86_GPU_STAGE_SELECT 2  /* choice, headers, gather */
+#define LZMA86_GPU_STAGE_TOTAL 3   /* the call; set without TIMINGS too */
+typedef struct Lzma86GpuStats {    /* 64 bytes */
+  uint32_t flags;                  /* in: LZMA86_GPU_TIMINGS or 0 */
+  uint32_t reserved;               /* 0 */
+  uint64_t candidates;             /* lanes of the encode batch */
+  uint64_t filtered;               /* streams that got a filtered candidate */
+  uint64_t encode_launches;        /* 1 unless workspace_limit cuts the batch */
+  uint64_t stage_ns[4];            /* LZMA86_GPU_STAGE_*: host clock, nanoseconds */
+} Lzma86GpuStats;
+
+/* Per stream the outcome is Lzma86_Encode's over a buffer of dst_cap bytes, bit
+ * for bit: a dst_cap below 14 is SZ_ERROR_OUTPUT_EOF with dest_len 0 and nothing
+ * written; each candidate is encoded into a capacity of dst_cap - 14; with AUTO
+ * the filtered candidate wins only when it fits and is strictly smaller than
+ * the unfiltered one (a tie goes to the unfiltered one, a lone fitting
+ * candidate is taken); when no candidate fits: SZ_ERROR_OUTPUT_EOF, dest_len 14,
+ * flag 0, the 14 header bytes written.  A filterMode other than NO and AUTO
+ * acts as YES, as in the reference.  The filter is x86_Convert from ip 0 with a
+ * fresh state over the whole source.  Differences: a level that normalises to a
+ * normal mode is SZ_ERROR_UNSUPPORTED unless the modes mask admits it
+ * (LzmaEncGpu_SetModes), a source of 2^31 bytes or more is SZ_ERROR_UNSUPPORTED,
+ * a dictSize above 1 << 30 is SZ_ERROR_PARAM; these three leave dest_len 0 and
+ * write nothing.  Bytes of dst outside [dst_off, dst_off + max(dest_len, 14))
+ * are never written.
+ *
+ * Lzma86Gpu_EncodeScratch (host only): the bytes of d_scratch a batch needs --
+ * the tables, the filtered copies of the sources, one slot of dst_cap - 14
+ * bytes per candidate and the encoder's workspace; SZ_ERROR_PARAM for n above
+ * 2^31 - 1.
+ * Lzma86Gpu_EncodeBatch: `descs` is host memory (the plan is host work), every
+ * other pointer device memory; d_scratch needs no initialisation.  One copy of
+ * the tables, then on `stream`: the stage copies and one BcjGpu_X86Batch, one
+ * LzmaEncGpu_EncodeBatch over all candidates (n lanes for NO and YES streams, 2
+ * per AUTO stream, in the planner's order), select and gather.  SZ_OK if
+ * everything was queued, SZ_ERROR_PARAM for a scratch_bytes below
+ * Lzma86Gpu_EncodeScratch's, SZ_ERROR_FAIL without a device. */
+SRes Lzma86Gpu_EncodeScratch(const Lzma86GpuStreamDesc *descs, size_t n, uint64_t *scratch_bytes);
+SRes Lzma86Gpu_EncodeBatch(const Lzma86GpuStreamDesc *descs, size_t n, const Byte *d_src,
+                           Byte *d_dst, void *d_scratch, uint64_t scratch_bytes,
+                           Lzma86GpuResult *d_results, void *stream);
+/* The same over host buffers: stages src and dst, plans as
+ * LzmaEncGpu_EncodeBatchHost does (streams longest first; as many encode
+ * launches as keep the encoder's workspace at or under workspace_limit, 0 = half
+ * of the free device memory; a stream's two candidates share a launch).
+ * SZ_ERROR_MEM if one stream's candidates alone exceed the limit or an
+ * allocation fails, SZ_ERROR_PARAM for a range outside src / dst.  stats may
+ * be NULL. */
+SRes Lzma86Gpu_EncodeBatchHost(const Lzma86GpuStreamDesc *descs, size_t n, const Byte *src,
+                               size_t src_size, Byte *dst, size_t dst_size,
+                               Lzma86GpuResult *results, uint64_t workspace_limit,
+                               Lzma86GpuStats *stats);
+
+/* Per stream the outcome is Lzma86_Decode's: a src_len below 14 is
+ * SZ_ERROR_INPUT_EOF, a flag byte above 1 SZ_ERROR_UNSUPPORTED (both with
+ * dest_len and src_len 0); else LzmaDecode of the payload with LZMA_FINISH_ANY
+ * into dst_cap bytes (src_len = 14 + the payload bytes read), and on SZ_OK with
+ * flag 1 x86_Convert in the decode direction over the dest_len bytes decoded.
+ * The host checks the headers: `headers` is host memory, 14 bytes per stream
+ * (stream i's first min(14, src_len) bytes at headers + 14 * i).
+ * Lzma86Gpu_DecodeScratch (host only): the bytes of d_scratch.
+ * Lzma86Gpu_DecodeBatch: descs and headers host memory, every other pointer
+ * device memory; on `stream`: one LzmaGpu_DecodeBatch over the payloads, the
+ * finish kernel, one BcjGpu_X86Batch over the outputs of the streams flagged 1. */
+SRes Lzma86Gpu_DecodeScratch(const Lzma86GpuStreamDesc *descs, size_t n, const Byte *headers,
+                             uint64_t *scratch_bytes);
+SRes Lzma86Gpu_DecodeBatch(const Lzma86GpuStreamDesc *descs, size_t n, const Byte *headers,
+                           const Byte *d_src, Byte *d_dst, void *d_scratch,
+                           uint64_t scratch_bytes, Lzma86GpuResult *d_results, void *stream);
+/* The same over host buffers (the headers are read from src). */
+SRes Lzma86Gpu_DecodeBatchHost(const Lzma86GpuStreamDesc *descs, size_t n, const Byte *src,
+                               size_t src_size, Byte *dst, size_t dst_size,
+                               Lzma86GpuResult *results);
+
+/* Lzma86.h:71-107 as one-item calls of the host forms.  Differences from the
+ * reference: those listed above; SZ_ERROR_FAIL without a device; on
+ * SZ_ERROR_OUTPUT_EOF dest holds the 14 header bytes only. */
+SRes Lzma86_Encode(Byte *dest, size_t *destLen, const Byte *src, size_t srcLen, int level,
+                   UInt32 dictSize, int filterMode);
+SRes Lzma86_GetUnpackSize(const Byte *src, SizeT srcLen, UInt64 *unpackSize);
+SRes Lzma86_Decode(Byte *dest, SizeT *destLen, const Byte *src, SizeT *srcLen);
 
 /* ---- 7z archives as folder batches ----------------
  * Replaces SzArEx_Open (7zIn.c:1314) + a SzArEx_Extract loop over every file

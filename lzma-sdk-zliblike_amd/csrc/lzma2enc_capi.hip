@@ -136,9 +136,12 @@ typedef HostBatch<LzmaEncGpuStreamDesc, LzmaEncGpuResult> Batch;
 
 // Uploads src (and dst when dst_init is given), lays the workspace out over
 // the longest-first order in as many launches as keep it at or under the
-// limit, and queues them on the null stream.  The caller synchronises.
+// limit, and queues them on the null stream; before(): what is queued between
+// the uploads and the first launch (0 on success).  The caller synchronises.
+template <class Before>
 SRes run_batch(const LzmaEncGpuStreamDesc* descs, size_t n, const Byte* src, size_t src_size,
-               const Byte* dst_init, size_t dst_size, uint64_t workspace_limit, Batch& b) {
+               const Byte* dst_init, size_t dst_size, uint64_t workspace_limit, Batch& b,
+               Before before) {
   static const char what[] = "LZMA2 encode batch";
   const SRes r = b.lay_out(
       what, descs, n, src_size, dst_size, workspace_limit,
@@ -148,8 +151,11 @@ SRes run_batch(const LzmaEncGpuStreamDesc* descs, size_t n, const Byte* src, siz
   // over the descriptors the device sees: the caller's ws_off is not looked at
   const std::vector<LzmaEncGpuStreamDesc> d = in_caller_order(descs, b.plan);
   const uint32_t kernels = lzmaenc_kernels(d.data(), n, lzma2enc_check);
+  bool first = true;
   return b.queue(what, d, true, src, src_size, dst_init, dst_size,
                  [&](uint32_t lo, uint32_t cnt) {
+                   if (first && before() != 0) return -1;
+                   first = false;
                    return lzma2encgpu_launch(b.desc.p, b.order.p, lo, cnt, uint32_t(n), b.src.p,
                                              b.dst.p, b.ws.p, b.res.p, LZMA_ENC_GPU_LANES_DEFAULT,
                                              nullptr, kernels);
@@ -207,17 +213,54 @@ struct Stream {
   std::vector<uint64_t> offsets;  // n + 1
   std::vector<LzmaEncGpuStreamDesc> descs;
   Batch b;
+  // with a filter chain: b.src is filtered in place before the encode, `plain`
+  // keeps the source as uploaded for the block checks
+  DevArr<uint8_t> plain;
+  FilterJob filter_jobs[LZMA_GPU_XZ_ENC_FILTERS_MAX];
+  const Byte* check_src() const { return plain.p ? plain.p : b.src.p; }
 };
+
+// The chain over every block of the uploaded source, first filter first in the
+// encode direction, one batch per filter; every block starts from a fresh state
+// at ip = the start offset.
+SRes queue_chain(Stream& s, size_t src_len, const LzmaGpuXzFilter* filters, unsigned num_filters) {
+  static const char what[] = "xz encode filters";
+  const size_t n = s.descs.size();
+  const SRes ar = alloc_all(what, s.plain, src_len);
+  if (ar != SZ_OK) return ar;
+  if (!hip_ok(hipMemcpyAsync(s.plain.p, s.b.src.p, src_len, hipMemcpyDeviceToDevice, nullptr),
+              what))
+    return SZ_ERROR_FAIL;
+  std::vector<uint64_t> off(n), len(n);
+  for (size_t i = 0; i < n; ++i) {
+    off[i] = s.descs[i].src_off;
+    len[i] = s.descs[i].src_len;
+  }
+  for (unsigned k = 0; k < num_filters; ++k) {
+    const std::vector<uint32_t> prop(n, filters[k].prop);
+    const SRes r =
+        queue_filter(what, s.filter_jobs[k], filters[k].id, s.b.src.p, off, len, prop.data(), 1);
+    if (r != SZ_OK) return r;
+  }
+  return SZ_OK;
+}
 
 // upload, one batch, compaction, download of offsets and stream
 SRes encode_stream(const Byte* src, size_t src_len, size_t block_size, const lzenc::Params& q,
-                   Stream& s) {
+                   Stream& s, const LzmaGpuXzFilter* filters = nullptr,
+                   unsigned num_filters = 0) {
   uint64_t slots_bytes = 0;
   const SRes cr = cut_blocks(src_len, block_size, q, s.descs, &slots_bytes);
   if (cr != SZ_OK) return cr;
   if (!ensure_device()) return SZ_ERROR_FAIL;
   const size_t n = s.descs.size();
-  const SRes rr = run_batch(s.descs.data(), n, src, src_len, nullptr, size_t(slots_bytes), 0, s.b);
+  SRes chain = SZ_OK;
+  const SRes rr = run_batch(s.descs.data(), n, src, src_len, nullptr, size_t(slots_bytes), 0, s.b,
+                            [&] {
+                              if (num_filters) chain = queue_chain(s, src_len, filters, num_filters);
+                              return chain == SZ_OK ? 0 : -1;
+                            });
+  if (chain != SZ_OK) return chain;
   if (rr != SZ_OK) return rr;
   DevArr<uint8_t> g_out;
   DevArr<uint64_t> g_off;
@@ -277,15 +320,36 @@ SRes block_checks(const Stream& s, unsigned check_size, std::vector<uint8_t>& ch
   }
   RangeChecks k;
   SRes r = k.prepare("xz encode", check_size, off, len);
-  if (r != SZ_OK || (r = k.launch(s.b.src.p)) != SZ_OK) return r;
+  if (r != SZ_OK || (r = k.launch(s.check_src())) != SZ_OK) return r;
   if (!hip_ok(hipDeviceSynchronize(), "xz block checks") ||
       !k.fetch(checks.data(), "download checks"))
     return SZ_ERROR_FAIL;
   return SZ_OK;
 }
 
+// the reader's rules for a chain (xz_capi.hip, BraState_SetProps XzDec.c:71-109)
+SRes check_chain(const LzmaGpuXzFilter* filters, unsigned num_filters) {
+  if (num_filters > LZMA_GPU_XZ_ENC_FILTERS_MAX) return SZ_ERROR_PARAM;
+  for (unsigned k = 0; k < num_filters; ++k) {
+    const uint32_t id = filters[k].id, prop = filters[k].prop;
+    if (id == 3) {
+      if (prop < 1 || prop > 256) return SZ_ERROR_PARAM;
+    } else if (id >= 4 && id <= 9) {
+      const uint32_t align = id == 6 ? 0xF : (id == 8 ? 1 : (id == 4 ? 0 : 3));
+      if (prop & align) return SZ_ERROR_PARAM;
+    } else {
+      set_error("xz encode: only delta and the branch converters (ids 3..9) are written");
+      return SZ_ERROR_UNSUPPORTED;
+    }
+  }
+  return SZ_OK;
+}
+
 SRes xz_encode(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
-               const CLzma2EncProps* props, unsigned check_type) {
+               const CLzma2EncProps* props, unsigned check_type, const LzmaGpuXzFilter* filters,
+               unsigned num_filters) {
+  const SRes cr = check_chain(filters, num_filters);
+  if (cr != SZ_OK) return cr;
   unsigned check_size;
   switch (check_type) {
     case LZMA_GPU_XZ_CHECK_NONE: check_size = 0; break;
@@ -305,24 +369,43 @@ SRes xz_encode(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
   Stream s;
   std::vector<uint8_t> checks;
   if (srcLen != 0) {
-    const SRes er = encode_stream(src, srcLen, norm.blockSize, q, s);
+    const SRes er = encode_stream(src, srcLen, norm.blockSize, q, s, filters, num_filters);
     if (er != SZ_OK) return er;
     const SRes kr = block_checks(s, check_size, checks);
     if (kr != SZ_OK) return kr;
   }
   const size_t n = s.descs.size();
-  // Xz_WriteHeader, XzBlock_WriteHeader (no size fields, one filter), Xz_WriteFooter
+  // Xz_WriteHeader, XzBlock_WriteHeader (no size fields; the chain, then LZMA2),
+  // Xz_WriteFooter
   const uint8_t flags[2] = {0, uint8_t(check_type)};
-  uint8_t bh[12] = {2, 0, 0x21, 1, prop, 0, 0, 0, 0, 0, 0, 0};
-  put32(bh + 8, crc32_host(bh, 8));
+  std::vector<uint8_t> bh{0, uint8_t(num_filters)};
+  for (unsigned k = 0; k < num_filters; ++k) {
+    bh.push_back(uint8_t(filters[k].id));
+    if (filters[k].id == 3) {
+      bh.push_back(1);
+      bh.push_back(uint8_t(filters[k].prop - 1));
+    } else if (filters[k].prop == 0) {
+      bh.push_back(0);
+    } else {
+      bh.push_back(4);
+      for (int i = 0; i < 4; ++i) bh.push_back(uint8_t(filters[k].prop >> (8 * i)));
+    }
+  }
+  bh.push_back(0x21);
+  bh.push_back(1);
+  bh.push_back(prop);
+  while (bh.size() & 3) bh.push_back(0);
+  bh[0] = uint8_t(bh.size() / 4);  // the size with the CRC, in words, less one
+  bh.resize(bh.size() + 4);
+  put32(bh.data() + bh.size() - 4, crc32_host(bh.data(), bh.size() - 4));
   std::vector<uint8_t> index{0};
   put_varint(index, n);
   uint64_t total = 12;
   for (size_t i = 0; i < n; ++i) {
     const uint64_t pack = s.offsets[i + 1] - s.offsets[i] + 1;  // the chunks and 0x00
-    put_varint(index, sizeof(bh) + pack + check_size);
+    put_varint(index, bh.size() + pack + check_size);
     put_varint(index, s.descs[i].src_len);
-    total += sizeof(bh) + ((pack + 3) & ~uint64_t(3)) + check_size;
+    total += bh.size() + ((pack + 3) & ~uint64_t(3)) + check_size;
   }
   while (index.size() & 3) index.push_back(0);
   index.resize(index.size() + 4);
@@ -339,8 +422,8 @@ SRes xz_encode(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
   p += 12;
   for (size_t i = 0; i < n; ++i) {
     const uint64_t len = s.offsets[i + 1] - s.offsets[i];
-    memcpy(p, bh, sizeof(bh));
-    p += sizeof(bh);
+    memcpy(p, bh.data(), bh.size());
+    p += bh.size();
     memcpy(p, s.bytes.data() + s.offsets[i], size_t(len));
     p += len;
     *p++ = 0;
@@ -440,7 +523,8 @@ extern "C" SRes Lzma2EncGpu_EncodeBatchHost(const LzmaEncGpuStreamDesc* descs, s
     if (!ensure_device()) return SZ_ERROR_FAIL;
     if (n == 0) return SZ_OK;
     Batch b;
-    SRes r = run_batch(descs, n, src, src_size, dst, dst_size, workspace_limit, b);
+    SRes r = run_batch(descs, n, src, src_size, dst, dst_size, workspace_limit, b,
+                       [] { return 0; });
     if (r != SZ_OK || (r = b.wait("LZMA2 encode batch", results, n)) != SZ_OK) return r;
     return b.download_dst(dst, 0, dst_size) ? SZ_OK : SZ_ERROR_FAIL;
   });
@@ -454,8 +538,15 @@ extern "C" SRes LzmaGpu_Lzma2EncodeHost(Byte* dest, SizeT* destLen, const Byte* 
 
 extern "C" SRes LzmaGpu_XzEncode(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
                                  const CLzma2EncProps* props, unsigned check_type) {
-  return guarded("xz encode: host allocation failed",
-                 [&]() { return xz_encode(dest, destLen, src, srcLen, props, check_type); });
+  return LzmaGpu_XzEncodeEx(dest, destLen, src, srcLen, props, check_type, nullptr, 0);
+}
+
+extern "C" SRes LzmaGpu_XzEncodeEx(Byte* dest, SizeT* destLen, const Byte* src, SizeT srcLen,
+                                   const CLzma2EncProps* props, unsigned check_type,
+                                   const LzmaGpuXzFilter* filters, unsigned num_filters) {
+  return guarded("xz encode: host allocation failed", [&]() {
+    return xz_encode(dest, destLen, src, srcLen, props, check_type, filters, num_filters);
+  });
 }
 
 extern "C" CLzma2EncHandle Lzma2Enc_Create(ISzAlloc* alloc, ISzAlloc* allocBig) {

@@ -22,8 +22,12 @@ After the timed region every block's result is checked for SZ_OK, the compacted
 stream's length against the sum, and a sample of blocks byte for byte against
 the reference.  --chunk-cost instead runs 4,096 text streams of 64 KiB through
 LzmaEncGpu_EncodeBatch and through the LZMA2 batch in alternating rounds and
-counts the chunks.  Lines are appended to --out (default
-profiles/lzma2enc/bench.jsonl, chunk_cost.jsonl)."""
+counts the chunks.  --xz-filter FILE instead takes the bytes of an x86 file
+repeated to the first buffer size and writes them with LzmaGpu_XzEncodeEx
+(CRC-64, the first block size) without a filter and with the x86 filter,
+alternating: time and file size of each (legs host_xz_exe and host_xz_exe_x86).
+Lines are appended to --out (default profiles/lzma2enc/bench.jsonl,
+chunk_cost.jsonl)."""
 import argparse
 import ctypes
 import json
@@ -242,6 +246,34 @@ def run_table(a, L, torch, np, native, emit):
                           seconds=round(s, 6), mb_per_s=round(k * block / 1e6 / s, 2)))
 
 
+def run_xz_filter(a, L, emit):
+    total = int(a.sizes.split(",")[0]) * MIB
+    block = int(a.blocks.split(",")[0])
+    with open(os.path.realpath(a.xz_filter), "rb") as f:
+        code = f.read()
+    buf = (code * (total // len(code) + 1))[:total]
+    cap = total + total // 256 + 65536
+    props = L.enc2_props(LEVEL, DICT, block_size=block)
+    tag = dict(level=LEVEL, buffer_mib=total // MIB, block_bytes=block,
+               blocks=(total + block - 1) // block, file=os.path.basename(a.xz_filter),
+               file_bytes=len(code))
+    sizes = {}
+
+    def leg(chain):
+        r, xz = L.XzEncodeEx(buf, props, 4, cap, chain)
+        assert r == 0, L.last_error()
+        sizes[bool(chain)] = len(xz)
+        return xz
+    assert L.XzDecode(leg([(4, 0)]), total)[:2] == (0, buf)      # warm-up and round trip
+    for rnd in range(max(a.reps, 2)):
+        for name, chain in (("host_xz_exe", []), ("host_xz_exe_x86", [(4, 0)])):
+            t0 = time.perf_counter()
+            leg(chain)
+            s = time.perf_counter() - t0
+            emit(dict(tag, leg=name, round=rnd, seconds=round(s, 6),
+                      mb_per_s=round(total / 1e6 / s, 2), xz_bytes=sizes[bool(chain)]))
+
+
 def count_chunks(L, g):
     """LZMA2 chunk headers in every block's slot."""
     n, cap = g["n"], g["cap"]
@@ -288,6 +320,8 @@ def main():
     ap.add_argument("--blocks", default="65536,262144,1048576")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--chunk-cost", action="store_true")
+    ap.add_argument("--xz-filter", default=None, metavar="FILE",
+                    help="the xz writer with and without the x86 filter over FILE's bytes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--level", type=int, default=1,
@@ -317,7 +351,9 @@ def main():
             print(line, flush=True)
             out.write(line + "\n")
             out.flush()
-        if a.chunk_cost:
+        if a.xz_filter:
+            run_xz_filter(a, L, emit)
+        elif a.chunk_cost:
             run_chunk_cost(a, L, torch, np, emit)
         else:
             run_table(a, L, torch, np, native, emit)

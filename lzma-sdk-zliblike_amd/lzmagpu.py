@@ -267,6 +267,32 @@ class EncResult(ctypes.Structure):
     _fields_ = [("res", ctypes.c_int32), ("_pad", ctypes.c_uint32), ("dest_len", ctypes.c_uint64)]
 
 
+class XzFilter(ctypes.Structure):
+    """LzmaGpuXzFilter: one filter of an xz block's chain in front of LZMA2."""
+    _fields_ = [("id", ctypes.c_uint32), ("prop", ctypes.c_uint32)]
+
+
+class Lzma86StreamDesc(ctypes.Structure):
+    """Lzma86GpuStreamDesc: one stream of an Lzma86 batch."""
+    _fields_ = [("src_off", ctypes.c_uint64), ("src_len", ctypes.c_uint64),
+                ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64),
+                ("level", ctypes.c_int32), ("dictSize", ctypes.c_uint32),
+                ("filterMode", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class Lzma86Result(ctypes.Structure):
+    """Lzma86GpuResult: Lzma86_Encode's / Lzma86_Decode's outcome for one stream."""
+    _fields_ = [("res", ctypes.c_int32), ("filter", ctypes.c_uint32),
+                ("dest_len", ctypes.c_uint64), ("src_len", ctypes.c_uint64)]
+
+
+class Lzma86Stats(ctypes.Structure):
+    """Lzma86GpuStats."""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("candidates", ctypes.c_uint64), ("filtered", ctypes.c_uint64),
+                ("encode_launches", ctypes.c_uint64), ("stage_ns", ctypes.c_uint64 * 4)]
+
+
 class EncSession(ctypes.Structure):
     """LzmaEncGpuSession (include/lzma_gpu.h, 200 bytes): a device-resident
     fast-mode encoder fed in pieces."""
@@ -538,6 +564,28 @@ _sig = {
                                        ctypes.POINTER(ISeqInStream), _P]),
     "LzmaGpu_XzEncode": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t,
                                         ctypes.POINTER(CLzma2EncProps), ctypes.c_uint]),
+    "LzmaGpu_XzEncodeEx": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t,
+                                          ctypes.POINTER(CLzma2EncProps), ctypes.c_uint,
+                                          ctypes.POINTER(XzFilter), ctypes.c_uint]),
+    "Lzma86Gpu_EncodeScratch": (ctypes.c_int, [ctypes.POINTER(Lzma86StreamDesc), ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_uint64)]),
+    "Lzma86Gpu_EncodeBatch": (ctypes.c_int, [ctypes.POINTER(Lzma86StreamDesc), ctypes.c_size_t, _P,
+                                             _P, _P, ctypes.c_uint64, _P, _P]),
+    "Lzma86Gpu_EncodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Lzma86StreamDesc), ctypes.c_size_t,
+                                                 _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                 ctypes.POINTER(Lzma86Result), ctypes.c_uint64,
+                                                 ctypes.POINTER(Lzma86Stats)]),
+    "Lzma86Gpu_DecodeScratch": (ctypes.c_int, [ctypes.POINTER(Lzma86StreamDesc), ctypes.c_size_t,
+                                               _P, ctypes.POINTER(ctypes.c_uint64)]),
+    "Lzma86Gpu_DecodeBatch": (ctypes.c_int, [ctypes.POINTER(Lzma86StreamDesc), ctypes.c_size_t, _P,
+                                             _P, _P, _P, ctypes.c_uint64, _P, _P]),
+    "Lzma86Gpu_DecodeBatchHost": (ctypes.c_int, [ctypes.POINTER(Lzma86StreamDesc), ctypes.c_size_t,
+                                                 _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                                 ctypes.POINTER(Lzma86Result)]),
+    "Lzma86_Encode": (ctypes.c_int, [_P, _sp, _P, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32,
+                                     ctypes.c_int]),
+    "Lzma86_GetUnpackSize": (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]),
+    "Lzma86_Decode": (ctypes.c_int, [_P, _sp, _P, _sp]),
     "LzmaGpu_7zWritePlan": (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _P,
                                            ctypes.c_size_t, _P, ctypes.c_size_t, _sp, _sp,
                                            ctypes.POINTER(ctypes.c_uint64)]),
@@ -1763,15 +1811,132 @@ def XzEncode(src, props, check, dest_cap):
     return r, d.raw[:dl.value] if r == SZ_OK else b""
 
 
-def xz_compress(data, check=1, level=1, dict_size=0, block_size=0, lc=-1, lp=-1, pb=-1):
-    """One xz stream, a block per block_size bytes.  Raises on an error."""
+def xz_filters(chain):
+    """[(id, prop)] as an XzFilter array (None for an empty chain) and its length."""
+    chain = list(chain)
+    if not chain:
+        return None, 0
+    arr = (XzFilter * len(chain))()
+    for k, (fid, prop) in enumerate(chain):
+        arr[k].id, arr[k].prop = fid, prop
+    return arr, len(chain)
+
+
+def XzEncodeEx(src, props, check, dest_cap, chain=()):
+    """LzmaGpu_XzEncodeEx with chain = [(id, prop)]: (res, file bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    arr, k = xz_filters(chain)
+    r = _lib.LzmaGpu_XzEncodeEx(d, ctypes.byref(dl), _buf(src), len(src), ctypes.byref(props),
+                                check, arr, k)
+    return r, d.raw[:dl.value] if r == SZ_OK else b""
+
+
+def xz_compress(data, check=1, level=1, dict_size=0, block_size=0, lc=-1, lp=-1, pb=-1, chain=()):
+    """One xz stream, a block per block_size bytes, chain = [(id, prop)] in front
+    of LZMA2.  Raises on an error."""
     bs = block_size or (1 << 20)
     blocks = len(data) // bs + 1
-    cap = 64 + len(data) + blocks * (block_bound(bs) - bs + 12 + 4 + 32 + 20)
-    r, out = XzEncode(data, enc2_props(level, dict_size, lc, lp, pb, block_size), check, cap)
+    cap = 64 + len(data) + blocks * (block_bound(bs) - bs + 12 + 4 + 32 + 20 + 24)
+    r, out = XzEncodeEx(data, enc2_props(level, dict_size, lc, lp, pb, block_size), check, cap,
+                        chain)
     if r != SZ_OK:
-        raise RuntimeError(f"LzmaGpu_XzEncode: {r}: {last_error()}")
+        raise RuntimeError(f"LzmaGpu_XzEncodeEx: {r}: {last_error()}")
     return out
+
+
+# ---------------------------------------------------------------- Lzma86
+
+LZMA86_HEADER_SIZE = 14
+SZ_FILTER_NO, SZ_FILTER_YES, SZ_FILTER_AUTO = 0, 1, 2
+LZMA86_TIMINGS = 1
+
+
+def lzma86_descs(items):
+    """items: dicts with src_off, src_len, dst_off, dst_cap and, for encoding,
+    level, dict_size, mode."""
+    arr = (Lzma86StreamDesc * max(len(items), 1))()
+    for i, it in enumerate(items):
+        arr[i].src_off, arr[i].src_len = it["src_off"], it["src_len"]
+        arr[i].dst_off, arr[i].dst_cap = it["dst_off"], it["dst_cap"]
+        arr[i].level, arr[i].dictSize = it.get("level", 1), it.get("dict_size", 0)
+        arr[i].filterMode = it.get("mode", SZ_FILTER_AUTO)
+    return arr
+
+
+def lzma86_encode_scratch(descs, n):
+    b = ctypes.c_uint64(0)
+    r = _lib.Lzma86Gpu_EncodeScratch(descs, n, ctypes.byref(b))
+    return r, b.value
+
+
+def lzma86_encode_batch_device(descs, n, d_src, d_dst, d_scratch, scratch_bytes, d_results,
+                               stream=0):
+    """Lzma86Gpu_EncodeBatch: descs on the host, the rest raw device pointers (ints)."""
+    return _lib.Lzma86Gpu_EncodeBatch(descs, n, d_src, d_dst, d_scratch, scratch_bytes, d_results,
+                                      stream or None)
+
+
+def lzma86_encode_batch_host(descs, n, src, dst, workspace_limit=0, stats=None):
+    """Lzma86Gpu_EncodeBatchHost: dst (bytes) is the output buffer's initial
+    contents.  Returns (res, results, dst bytes)."""
+    res = (Lzma86Result * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.Lzma86Gpu_EncodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res,
+                                       workspace_limit,
+                                       ctypes.byref(stats) if stats is not None else None)
+    return r, res, d.raw[:len(dst)]
+
+
+def lzma86_headers(descs, n, src):
+    """The 14 header bytes per stream the decode calls take, from the host copy."""
+    out = bytearray(14 * max(n, 1))
+    for i in range(n):
+        h = src[descs[i].src_off:descs[i].src_off + min(14, descs[i].src_len)]
+        out[14 * i:14 * i + len(h)] = h
+    return bytes(out)
+
+
+def lzma86_decode_scratch(descs, n, headers):
+    b = ctypes.c_uint64(0)
+    r = _lib.Lzma86Gpu_DecodeScratch(descs, n, headers, ctypes.byref(b))
+    return r, b.value
+
+
+def lzma86_decode_batch_device(descs, n, headers, d_src, d_dst, d_scratch, scratch_bytes,
+                               d_results, stream=0):
+    return _lib.Lzma86Gpu_DecodeBatch(descs, n, headers, d_src, d_dst, d_scratch, scratch_bytes,
+                                      d_results, stream or None)
+
+
+def lzma86_decode_batch_host(descs, n, src, dst):
+    res = (Lzma86Result * max(n, 1))()
+    d = ctypes.create_string_buffer(bytes(dst), max(len(dst), 1))
+    r = _lib.Lzma86Gpu_DecodeBatchHost(descs, n, _buf(src), len(src), d, len(dst), res)
+    return r, res, d.raw[:len(dst)]
+
+
+def Lzma86_Encode(src, dest_cap, level=1, dict_size=0, mode=SZ_FILTER_AUTO):
+    """The drop-in: (res, destLen, stream bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    res = _lib.Lzma86_Encode(d, ctypes.byref(dl), _buf(src), len(src), level, dict_size, mode)
+    return res, dl.value, d.raw[:dl.value]
+
+
+def Lzma86_GetUnpackSize(src):
+    v = ctypes.c_uint64(0)
+    res = _lib.Lzma86_GetUnpackSize(_buf(src), len(src), ctypes.byref(v))
+    return res, v.value
+
+
+def Lzma86_Decode(src, dest_cap):
+    """The drop-in: (res, destLen, srcLen, bytes)."""
+    d = ctypes.create_string_buffer(max(dest_cap, 1))
+    dl = ctypes.c_size_t(dest_cap)
+    sl = ctypes.c_size_t(len(src))
+    res = _lib.Lzma86_Decode(d, ctypes.byref(dl), _buf(src), ctypes.byref(sl))
+    return res, dl.value, sl.value, d.raw[:dl.value] if res == SZ_OK else b""
 
 
 def session_probs_bytes(props):
