@@ -423,7 +423,8 @@ typedef struct LzmaGpuPlanOptions {
  * (LZGPU_ILV=0) */
 #define LZMA_GPU_PLAN_NO_ILV 16u
 /* A/B: interleaved rows for throughput waves of any width up to 64 lanes, not
- * only whole 32-lane groups (LZGPU_ILV_ANY=1) */
+ * only whole 32-lane groups (LZGPU_ILV_ANY=1); a class whose 32-lane row of LDS
+ * slices would not fit a CU's LDS keeps its per-lane slices */
 #define LZMA_GPU_PLAN_ILV_ANY 32u
 /* Default: a single-class batch of 17 to 63 streams per CU in the latency
  * regime (a strong-scaling share, e.g. 8,192 x 4 KiB on 256 CUs) runs waves

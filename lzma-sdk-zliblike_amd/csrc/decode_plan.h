@@ -341,7 +341,13 @@ inline SRes plan_batch(LzmaGpuStreamDesc* descs, size_t n, uint32_t* order, Lzma
         break;
       }
     const bool ilv_any = (o.flags & LZMA_GPU_PLAN_ILV_ANY) != 0;
+    // interleaved LDS slices take whole 32-lane rows (decode_launch_shape): a
+    // narrow workgroup of a wide table (2 lanes at lc + lp = 4: 32 x 8,676 bytes)
+    // would ask for more LDS than a CU has, so it keeps its per-lane slices
+    const size_t ilv_lds = size_t((c.lanes_per_group + lzgpu::kIlv - 1) / lzgpu::kIlv * lzgpu::kIlv) *
+                           c.lds_cells_per_lane * 2;
     if (!(o.flags & LZMA_GPU_PLAN_NO_ILV) && c.lds_mask == LZGPU_LDS_MASK &&
+        ilv_lds <= kLdsBytesPerCu &&
         (c.lanes_per_group == 32 || c.lanes_per_group == 64 || (ilv_any && c.lanes_per_group <= 64))) {
       // lane-interleaved global sections: one column per resident lane (the
       // lanes keep it across the streams they take from the queue); config 3

@@ -16,6 +16,18 @@ Small test batches would only ever reach the last two, so:
     and the per-stream result invariants.
 
 Bit-exact throughout: output bytes and {res, status, destLen, srcLen}.
+
+This module forces PLACEMENTS (_opts, _check_plan), not builds: which of the 42
+rows of the kernel table a placement's class launches -- the W of its
+__launch_bounds__ and the build with or without the LZMA2 chunk walker --
+follows the plan's register budget and, for one-stream workgroups, the batch
+size against the device's CU count.  On a 256-CU device the hand-made batch
+reaches nine of them under these options: lds-w1-40000105-k0,
+lds-w2-40000105-k0, lds-w2-105-k0, lds-w1-105-k1, lds-w2-105-k1, dup-w4-19f-k1,
+coop-w4-880007ff-k0, coop-w4-800001bf-k0 and coop-w4-800001bf-k1 (ids
+family-W-placement-K2, as in tests/test_decode_plan.py).  tests/
+test_handmade_rows.py forces the BUILDS: the hand-made cases and the golden
+vectors that fit through every row, each launch's row asserted.
 """
 import ctypes
 import lzma
