@@ -195,6 +195,12 @@ typedef __attribute__((address_space(1))) uint32_t gu32;
 // to its column with cell arithmetic scaled by the row length.
 constexpr uint32_t kIlvBit = 0x40000000u;
 constexpr uint32_t kIlv = 32u;
+// Not a placement: the throughput kernel's W = 4 instantiations pass it down
+// so that mp_on (round 9) stays off in them -- they spill at 128 VGPRs, the
+// batches held across decisions would add 50 to 90 bytes of scratch each, and
+// no benchmark measures them.  kRowBits: the bits a placement test ignores.
+constexpr uint32_t kMpOffBit = 0x10000000u;
+constexpr uint32_t kRowBits = kIlvBit | kMpOffBit;
 struct GS {
   gu16* p;
   __device__ __forceinline__ GS operator+(uint32_t k) const { return GS{p + kIlv * k}; }
@@ -222,6 +228,9 @@ struct LS {
 //   LZGPU_LIT_BATCH    literals decoded per pass of the symbol loop before a
 //                      lane's match path runs (1 = one symbol per pass)
 //   LZGPU_PROF         profiling build: wave-uniform cycle stamps per region
+//   LZGPU_MP           the throughput match path's load batches (mp_on, round
+//                      9): 1 length front, 2 LenHigh in three batches, 4 the
+//                      distance tail's early batch (0 = round 8's path)
 // The code shapes measured and rejected in rounds 1-2 (branch-free NORMALIZE,
 // tree child-pair prefetch, two-round-trip literal trees, unified plain /
 // matched literals, literal write-combining, byte-wise and batched-tail copies,
@@ -942,7 +951,36 @@ __host__ __device__ constexpr bool lit_addr_on() {
 #endif
 template <uint32_t M>
 __host__ __device__ constexpr bool fuse_on(uint32_t bit) {
-  return (LZGPU_FUSE & bit) != 0u && (M & ~kIlvBit) == LZGPU_LDS_MASK;
+  return (LZGPU_FUSE & bit) != 0u && (M & ~kRowBits) == LZGPU_LDS_MASK;
+}
+// The match path's dependent global round trips (round 9): a
+// wave's entry walks choice -> choice2 -> length tree -> slot tree (two
+// batches) -> distance tail, every step a load batch whose address needs the
+// step before, each behind the earlier decisions' stores in the in-order
+// vmcnt queue.  With lane-interleaved rows the cells that lanes share sit in
+// one 64-byte row, so loading more cells per batch costs few extra lines.
+// One bit per form; a load moves ahead of decisions that cannot store to its
+// cells, never the decisions, their order, the input bytes or the updates:
+//   1 length front: choice, choice2 and the low and mid trees of the lane's
+//     posState in ONE batch on the per-lane coder base (Len or RepLen), issued
+//     when IsRep is decided, ahead of the rep-distance bits (LDS), and decided
+//     from registers (F1's one walk for low and mid kept)
+//   2 LenHigh in three batches (tree8_g: 3 + 3 + 2 levels) instead of eight
+//     dependent cells
+//   4 distance tail: the reverse tree's first batch (seven cells on the
+//     per-lane base, SpecPos + sp or Align) issued before the direct bits and
+//     decided behind them; the last one or two levels from one batch
+// (8, the slot tree's top issued early, was not built: DESIGN.md §4 round 9.)
+// (A fourth tail level from the early batch, Align as sub4, measured inside
+// three times the A/B spread and was removed.)
+// Gated like fuse_on: the throughput placement only, both row layouts, and
+// off under kMpOffBit (the W = 4 instantiations).
+#ifndef LZGPU_MP
+#define LZGPU_MP 7
+#endif
+template <uint32_t M>
+__host__ __device__ constexpr bool mp_on(uint32_t bit) {
+  return (LZGPU_MP & bit) != 0u && (M & kMpOffBit) == 0u && (M & ~kRowBits) == LZGPU_LDS_MASK;
 }
 // Some active lane of the wave wants the fused walk.  The host emulation is
 // one lane wide: there -DLZGPU_FUSE_EMU_ALL=1 (tests only) answers "yes" for
@@ -999,7 +1037,7 @@ __host__ __device__ constexpr bool def_on() {
 // removed in round 5 with the other rejected shapes.
 template <uint32_t M>
 struct BulkReaderFor {
-  static constexpr uint32_t m = M & ~kIlvBit;
+  static constexpr uint32_t m = M & ~kRowBits;
   static constexpr bool q = m == LZGPU_LDS_MASK || m == (LZGPU_LDS_MASK_LAT | kCoopBit) ||
                             m == (LZGPU_LDS_MASK_ALL | kCoopBit);
   // the throughput placement's own reader (LZGPU_READER)
@@ -1017,7 +1055,7 @@ struct BulkReaderFor {
 // within noise either way: profiles/r02_ilv/mbpf_latency_ab.log)
 template <uint32_t M>
 __host__ __device__ constexpr bool mb_pf_on() {
-  return ((M & kCoopBit) != 0u) || ((M & ~kIlvBit) == LZGPU_LDS_MASK);
+  return ((M & kCoopBit) != 0u) || ((M & ~kRowBits) == LZGPU_LDS_MASK);
 }
 
 // checkpoint hooks for readers without them: every NORMALIZE checks
@@ -1382,6 +1420,23 @@ struct Rc {
     const uint32_t b1 = bit_v(b0 ? c[2] : c[1], probs + m);
     m = 2 * m + b1;
     const uint32_t p2 = b0 ? (b1 ? c[6] : c[5]) : (b1 ? c[4] : c[3]);
+    const uint32_t b2 = bit_v(p2, probs + m);
+    return 2 * m + b2;
+  }
+  // dec3 on seven values (c1: the root's cell, c2 / c3 its children, c4..c7
+  // theirs) instead of an array: where the batch is loaded well ahead of its
+  // decisions (mp_on), dec3's choice between array cells kept the array in
+  // scratch memory (32 bytes per site in the throughput builds).
+  template <class P>
+  __device__ __forceinline__ uint32_t dec3_v(P probs, uint32_t root, uint32_t c1, uint32_t c2,
+                                             uint32_t c3, uint32_t c4, uint32_t c5, uint32_t c6,
+                                             uint32_t c7) {
+    if constexpr (kGlobP<P>) wstamp();
+    const uint32_t b0 = bit_v(c1, probs + root);
+    uint32_t m = 2 * root + b0;
+    const uint32_t b1 = bit_v(b0 ? c3 : c2, probs + m);
+    m = 2 * m + b1;
+    const uint32_t p2 = b0 ? (b1 ? c7 : c6) : (b1 ? c5 : c4);
     const uint32_t b2 = bit_v(p2, probs + m);
     return 2 * m + b2;
   }
@@ -1967,7 +2022,20 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
 #if LZGPU_PROF && !defined(LZGPU_HOST_EMU)
   uint64_t t_prof = lz_clock();
 #endif
+#if LZGPU_PROF == 1 && !LZGPU_PROF_DRAIN && !defined(LZGPU_HOST_EMU)
+  // prof[13] in the throughput placement (which writes it nowhere else): the
+  // wave's time from the end of a literal batch to the next pass's start --
+  // the match path -- booked by EVERY live lane, as prof[17] books the
+  // iterations; prof[1] / prof[2] / prof[8..10] are summed over the lanes that
+  // entered the path only, the others book the same time under prof[0]
+  uint64_t t_mp = 0;
+#endif
   do {
+#if LZGPU_PROF == 1 && !LZGPU_PROF_DRAIN && !defined(LZGPU_HOST_EMU)
+    if constexpr ((M & ~kRowBits) == LZGPU_LDS_MASK) {
+      if (t_mp != 0) s.prof[13] += lz_clock() - t_mp;
+    }
+#endif
     uint32_t lcoder_is_rep;
     if constexpr (kUL) {
       // one symbol per pass, kind and loop exit as uniform branches
@@ -2054,6 +2122,9 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
 #endif
     }
     LZ_PROF_MARK(s, 0, t_prof);
+#if LZGPU_PROF == 1 && !LZGPU_PROF_DRAIN && !defined(LZGPU_HOST_EMU)
+    t_mp = lz_clock();
+#endif
 #if LZGPU_PROF == 2 && !defined(LZGPU_HOST_EMU)
     {
       const uint64_t mm = __builtin_amdgcn_ballot_w64(is_match && !stop);
@@ -2087,7 +2158,27 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
 #endif
     const uint64_t tm0 = lz_clock();
 #endif
-    if (lz_br<kU>(!rc.bit(T.template at<S_REP>(st)))) {
+    const uint32_t is_rep = rc.bit(T.template at<S_REP>(st));
+    // the length front's cells (mp_on 1): choice, choice2, the low and the mid
+    // tree of this posState on the lane's coder base
+    uint32_t lf_ch = 0, lf_ch2 = 0, lf_lo[7], lf_mid[7];
+    if constexpr (mp_on<M>(1u)) {
+      // Loaded here, ahead of the rep-distance bits: those decide and store
+      // cells of IsRepG0..G2 (LDS) and IsRep0Long (its own global section)
+      // only, and every path from here to the length coder makes no other
+      // decision, so no store can reach a Len / RepLen cell before its use.
+      // A lane that leaves before the length coder (short rep, data error)
+      // has loaded sixteen cells of its own RepLen column for nothing.
+      auto lb = T.g(is_rep ? T.L.o[S_REPLEN] : T.L.o[S_LEN]);
+      lf_ch = lb[0];
+      lf_ch2 = lb[1];
+      rc.load7(lb + 2 + (ps << 3), 1, lf_lo);
+      rc.load7(lb + 2 + (8u << pb) + (ps << 3), 1, lf_mid);
+      LZ_WCLS(rc, W_LEN);
+      rc.wstamp();
+      LZ_WCLS(rc, W_REP);
+    }
+    if (lz_br<kU>(!is_rep)) {
       st += 12;
       lcoder_is_rep = 0;
     } else {
@@ -2164,7 +2255,7 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
       if constexpr (!len_lds) {
         // global length coder: the choice bits and the low tree load together,
         // the mid tree only behind choice = 1
-        if constexpr ((M & ~kIlvBit) != LZGPU_LDS_MASK) {
+        if constexpr ((M & ~kRowBits) != LZGPU_LDS_MASK) {
         // choice, choice2 and both 3-level trees of this posState in ONE load
         // batch; only lengths >= 18 go back to memory (LenHigh, 3 batches)
         auto lo_t = lbase + 2 + (ps << 3);
@@ -2182,6 +2273,28 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           LZ_WCLS(rc, W_LENHI);
           len = 16 + rc.tree8_g(T.template at<S_LENHI>(lcoder_is_rep << 8)) - 256;
         }
+        } else if constexpr (mp_on<M>(1u)) {
+        // the length front from the batch issued at IsRep: choice, choice2
+        // behind choice = 1, then F1's ONE 3-level walk for every lane with a
+        // short length, its seven cells selected from the low or the mid tree
+        const uint32_t c1 = rc.bit_v(lf_ch, lbase);
+        uint32_t c2 = 0;
+        if (c1) c2 = rc.bit_v(lf_ch2, lbase + 1);
+        if (!c2) {
+          auto len_t = lbase + (2 + (c1 ? (8u << pb) : 0u) + (ps << 3));
+          auto pick = [&](int k) {
+            const uint32_t vm = lf_mid[k], vl = lf_lo[k];
+            return c1 ? vm : vl;
+          };
+          len = (c1 ? 8u : 0u) + rc.dec3_v(len_t, 1, pick(0), pick(1), pick(2), pick(3), pick(4),
+                                           pick(5), pick(6)) - 8;
+        } else {
+          LZ_WCLS(rc, W_LENHI);
+          if constexpr (mp_on<M>(2u))
+            len = 16 + rc.tree8_g(T.template at<S_LENHI>(lcoder_is_rep << 8)) - 256;
+          else
+            len = 16 + rc.template tree<8>(T.template at<S_LENHI>(lcoder_is_rep << 8));
+        }
         } else if constexpr (fuse_on<M>(1u)) {
         // F1: choice, then choice2 for the lanes behind choice = 1, then ONE
         // 3-level walk for every lane with a short length -- the low tree or
@@ -2196,7 +2309,10 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           len = (c1 ? 8u : 0u) + rc.sub3(len_t, 1) - 8;
         } else {
           LZ_WCLS(rc, W_LENHI);
-          len = 16 + rc.template tree<8>(T.template at<S_LENHI>(lcoder_is_rep << 8));
+          if constexpr (mp_on<M>(2u))
+            len = 16 + rc.tree8_g(T.template at<S_LENHI>(lcoder_is_rep << 8)) - 256;
+          else
+            len = 16 + rc.template tree<8>(T.template at<S_LENHI>(lcoder_is_rep << 8));
         }
         } else {
         const uint32_t ch = lbase[0];
@@ -2208,7 +2324,10 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           len = 8 + rc.sub3(lbase + 2 + (8u << pb) + (ps << 3), 1) - 8;
         else {
           LZ_WCLS(rc, W_LENHI);
-          len = 16 + rc.template tree<8>(T.template at<S_LENHI>(lcoder_is_rep << 8));
+          if constexpr (mp_on<M>(2u))
+            len = 16 + rc.tree8_g(T.template at<S_LENHI>(lcoder_is_rep << 8)) - 256;
+          else
+            len = 16 + rc.template tree<8>(T.template at<S_LENHI>(lcoder_is_rep << 8));
         }
         }
       } else {
@@ -2270,6 +2389,17 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           // batch where the lane has that many, the rest one by one
           const bool spec = slot < 14;
           uint32_t rb_off, rb_n;
+          uint32_t rb_c[7];
+          if constexpr (mp_on<M>(4u)) {
+            // The walk's first batch issued before the direct bits: the base
+            // is known with the slot (SpecPos + sp, or Align), and the direct
+            // bits decide no adaptive cell, so nothing is stored between this
+            // load and its use.  Seven cells from any SpecPos base stay inside
+            // the SpecPos section (the last base is 82 of 114 cells); lanes
+            // with slot < 4 are not here.
+            rc.load7(T.g(spec ? T.L.o[S_SPEC] + ((dist << nbits) - slot - 1) : T.L.o[S_ALIGN]), 1,
+                     rb_c);
+          }
           if (!spec) {
             nbits -= 4;
             do rc.direct(dist); while (--nbits != 0);
@@ -2289,10 +2419,36 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           auto rb_t = T.g(rb_off);
           uint32_t mask = 1, node = 1;
           if (rb_n >= 3) {
-            node = rc.sub3(rb_t, 1);
+            if constexpr (mp_on<M>(4u))
+              node = rc.dec3_v(rb_t, 1, rb_c[0], rb_c[1], rb_c[2], rb_c[3], rb_c[4], rb_c[5],
+                               rb_c[6]);
+            else
+              node = rc.sub3(rb_t, 1);
             dist |= ((node >> 2) & 1u) | (((node >> 1) & 1u) << 1) | ((node & 1u) << 2);
             mask = 8;
             rb_n -= 3;
+          }
+          if constexpr (mp_on<M>(4u)) {
+            // the last one or two levels (two: SpecPos with 2 or 5 bits) from
+            // one batch -- sub2's cells, where a lane with one level left
+            // loads its node's cell three times instead of children it has
+            // not got (Align ends at cell 15).  The children are other cells
+            // than the node, so the first decision's store does not reach them.
+            if (rb_n != 0) {
+              const bool two = rb_n == 2;
+              const uint32_t p0 = rb_t[node];
+              const uint32_t p1 = rb_t[two ? 2 * node : node];
+              const uint32_t p2 = rb_t[two ? 2 * node + 1 : node];
+              rc.wstamp();
+              const uint32_t b0 = rc.bit_v(p0, rb_t + node);
+              node = (node << 1) | b0;
+              dist |= b0 ? mask : 0u;
+              if (two) {
+                const uint32_t b1 = rc.bit_v(b0 ? p2 : p1, rb_t + node);
+                dist |= b1 ? (mask << 1) : 0u;
+              }
+              rb_n = 0;
+            }
           }
           while (rb_n != 0) {
             const uint32_t b = rc.bit(rb_t + node);
@@ -2322,7 +2478,7 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
               mask = 8;
               nbits -= 3;
             }
-            if constexpr ((M & ~kIlvBit) != LZGPU_LDS_MASK) if (nbits == 2) {
+            if constexpr ((M & ~kRowBits) != LZGPU_LDS_MASK) if (nbits == 2) {
               // the last two bits in one batch as well
               const uint32_t n2 = rc.sub2(T.template at<S_SPEC>(sp), node);
               dist |= (((n2 >> 1) & 1u) ? mask : 0u) | ((n2 & 1u) ? (mask << 1) : 0u);
@@ -2353,7 +2509,7 @@ __device__ __forceinline__ int lz_run(LzStateT<Lo>& s, uint64_t limit, Rd& rd,
           uint32_t node = 1;
           LZ_WCLS(rc, W_ALIGN);
           if constexpr (((M >> S_ALIGN) & 1u) == 0u) {
-            if constexpr ((M & ~kIlvBit) != LZGPU_LDS_MASK) {
+            if constexpr ((M & ~kRowBits) != LZGPU_LDS_MASK) {
               // all four reverse bits from one batch of the 15 cells
               node = rc.sub4(T.template at<S_ALIGN>(0), 1);
               dist |= ((node >> 3) & 1u) | (((node >> 2) & 1u) << 1) |

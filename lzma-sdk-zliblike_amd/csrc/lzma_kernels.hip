@@ -100,7 +100,9 @@ __global__ void __launch_bounds__(64, W) lzgpu_decode_lds_kernel(
   while (idx < n) {
     const uint32_t id = order ? order[idx] : idx;
     const LzmaGpuStreamDesc d = descs[id];
-    results[id] = lane_decode_lds<M, K2>(d, src, dst, ws, lo, stride, gcol);
+    // (W = 4 of the throughput placement: without the round-9 load batches)
+    constexpr uint32_t ML = (W > 2 && (M & ~kIlvBit) == LZGPU_LDS_MASK) ? (M | kMpOffBit) : M;
+    results[id] = lane_decode_lds<ML, K2>(d, src, dst, ws, lo, stride, gcol);
     idx = start + atomicAdd(queue, 1u);
   }
 }
