@@ -69,7 +69,7 @@ struct Folder {
   std::vector<uint64_t> unpack_sizes;
   bool crc_defined = false;
   uint32_t crc = 0;
-  uint32_t num_unpack_streams = 1;
+  uint32_t num_unpack_streams = 0;  // SzFolder_Init: 1 only once a SubStreamsInfo is read
   uint32_t num_out() const {
     uint32_t n = 0;
     for (const Coder& c : coders) n += c.nout;
@@ -400,8 +400,13 @@ SRes read_substreams(Sd& s, Ar& a, SubStreams& ss) {
   for (const Folder& f : a.folders)
     if (f.num_unpack_streams != 1 || !f.crc_defined) n_digests += f.num_unpack_streams;
   si = 0;
+  bool have_crc = false;
   for (;;) {
     if (t == kCRC) {
+      // a second kCRC section: the reference goes on writing behind its digest
+      // arrays (si is not reset, 7zIn.c:814-843)
+      if (have_crc && ss.n != 0) return SZ_ERROR_ARCHIVE;
+      have_crc = true;
       std::vector<Byte> d2;
       std::vector<uint32_t> c2;
       RINOK7(hash_digests(s, n_digests, &d2, &c2));
@@ -502,6 +507,11 @@ SRes fill(Archive& x) {
       }
     }
     x.file_folder[i] = fi;
+    // the reference decodes this folder for the file and indexes PackSizes
+    // unchecked (7zIn.c:1373-1375, 7zDec.c:385-386): a folder that needs more
+    // pack sizes than PackInfo gave
+    if (uint64_t(x.folder_start_pack[fi]) + a.folders[fi].pack_streams.size() > a.pack_sizes.size())
+      return SZ_ERROR_ARCHIVE;
     if (empty) continue;
     if (++in_folder >= a.folders[fi].num_unpack_streams) {
       ++fi;
@@ -747,7 +757,9 @@ Job make_job(const Archive& x, const Ar& a, uint32_t fi, uint64_t start, const B
     j.rc_avail = avail(j.rc_off, j.rc_size);
     j.pack_off = j.units[2].pack_off;  // the main stream's coder
     j.pack_size = j.units[2].pack_size;
-    j.res = SZ_OK;
+    // coder 0 decodes first: what fails it before decoding fails the folder
+    // (later coders' checks only count once the ones before them have decoded)
+    j.res = j.units[0].pre;
     return j;
   } else {
     return j;
@@ -772,6 +784,12 @@ uint64_t bcj2_temp_bytes(const std::vector<Job>& jobs) {
 // SzDecodeLzma / SzDecodeLzma2 acceptance (7zDec.c:161-168, 209-216): the
 // whole output, the whole pack stream, a finished status
 static SRes accept(const Unit& u, const LzmaGpuResult& q) {
+  // SzDecodeLzma and SzDecodeLzma2 never return SZ_ERROR_INPUT_EOF: input that
+  // runs out ends as SZ_ERROR_DATA (7zDec.c:157-163, 207-212).  The batch
+  // decoder says INPUT_EOF for an LZMA stream of fewer than the five bytes a
+  // range coder starts with; the reference feeds what there is, gets nothing
+  // decoded from an empty second look and says DATA.  Mapped for both kinds.
+  if (q.res == SZ_ERROR_INPUT_EOF) return SZ_ERROR_DATA;
   if (q.res != SZ_OK) return q.res;
   const bool status_ok = u.method == kLzma ? (q.status == LZMA_STATUS_FINISHED_WITH_MARK ||
                                               q.status == LZMA_STATUS_MAYBE_FINISHED_WITHOUT_MARK)
@@ -1058,6 +1076,9 @@ SRes open_archive(const Byte* arc, size_t size, Archive& x) {
     RINOK7(read_streams_info(s, &start, hx.db, ss, &have_ss));
     start += kStartHeader;
     if (hx.db.folders.size() != 1) return SZ_ERROR_ARCHIVE;
+    // no PackInfo, or fewer sizes than the folder has pack streams: the
+    // reference reads PackSizes unchecked (7zIn.c:1181, 7zDec.c:385-386)
+    if (hx.db.folders[0].pack_streams.size() > hx.db.pack_sizes.size()) return SZ_ERROR_ARCHIVE;
     RINOK7(sizes_checked(hx.db));
     hx.folder_start_pack.assign(1, 0);
     hx.flags = x.flags;

@@ -23,7 +23,19 @@
 #include "Alloc.h"
 #include "LzmaDec.h"
 
-static void *shim_alloc(void *p, size_t n) { (void)p; return malloc(n ? n : 1); }
+/* the largest request the reference made since the last reset: the hand-made
+ * 7z cases must not hang on whether a huge malloc succeeds (ref_shim_max_alloc) */
+static size_t g_shim_max_alloc = 0;
+static void *shim_alloc(void *p, size_t n) {
+  (void)p;
+  if (n > g_shim_max_alloc) g_shim_max_alloc = n;
+  return malloc(n ? n : 1);
+}
+unsigned long long ref_shim_max_alloc(int reset) {
+  unsigned long long m = g_shim_max_alloc;
+  if (reset) g_shim_max_alloc = 0;
+  return m;
+}
 static void shim_free(void *p, void *a) { (void)p; free(a); }
 static ISzAlloc g_shim_alloc = {shim_alloc, shim_free};
 
@@ -97,10 +109,14 @@ unsigned long long ref_crc64(const unsigned char *data, size_t size) {
  * through LookToRead (non-lookahead, as 7zMain.c:326 sets it up), then
  * SzArEx_Extract (7zIn.c:1322) for every file with a fresh folder cache
  * (blockIndex reset after an error, so each file's result stands alone).
- * Files that extract OK are appended to out; file_res / file_size per file;
- * names = the raw UTF-16LE FileNames buffer.  Returns SzArEx_Open's result.
+ * Files that extract OK are appended to out; file_res / file_size per file
+ * (REF_7Z_OUTSIDE where the reference reports OK for a range outside its own
+ * buffer); names = the raw UTF-16LE FileNames buffer.  Returns SzArEx_Open's
+ * result.
  */
 #include "7z.h"
+
+#define REF_7Z_OUTSIDE (-1)
 
 typedef struct {
   ISeekInStream s;
@@ -164,9 +180,13 @@ int ref_7z_extract(const unsigned char *arc, size_t size, unsigned char *out, si
       size_t offset = 0, got = 0;
       SRes r = SzArEx_Extract(&db, &look.s, i, &block, &buf, &buf_size, &offset, &got,
                               &g_shim_alloc, &g_shim_alloc);
+      /* a substream size that wrapped (7zIn.c:792) can pass SzArEx_Extract's
+         offset + size check (7zIn.c:1395, a sum that wraps back): the range it
+         then reports lies outside its own buffer and is not read here */
+      if (r == SZ_OK && (got > buf_size || offset > buf_size - got)) r = REF_7Z_OUTSIDE;
       file_res[i] = r;
       file_size[i] = db.db.Files[i].Size;
-      if (r == SZ_OK && pos + got <= cap) {
+      if (r == SZ_OK && got != 0 && got <= cap - pos) {
         memcpy(out + pos, buf + offset, got);
         pos += got;
       }
@@ -177,6 +197,62 @@ int ref_7z_extract(const unsigned char *arc, size_t size, unsigned char *out, si
   SzArEx_Free(&db, &g_shim_alloc);
   quiet_end(saved);
   *out_len = pos;
+  return res;
+}
+
+/*
+ * What SzArEx_Open made of the header (the structures SzArEx_Extract walks):
+ * per folder five UInt64s {NumCoders, SzFolder_GetUnpackSize, UnpackCRCDefined,
+ * UnpackCRC, NumUnpackStreams}, per file five UInt32s {HasStream, IsDir,
+ * CrcDefined, Crc, FileIndexToFolderIndexMap}; a CRC that is not defined is
+ * given as 0 (the reference leaves its value unset).  Counts are complete even
+ * where the arrays are too small.  Returns SzArEx_Open's result.
+ */
+int ref_7z_info(const unsigned char *arc, size_t size, unsigned long long *folders,
+                size_t folder_cap, unsigned *n_folders, unsigned *files, size_t file_cap,
+                unsigned *n_files) {
+  ShimMemSeek ms;
+  CLookToRead look;
+  CSzArEx db;
+  SRes res;
+  UInt32 i;
+  int saved;
+  xz_tables();
+  ms.s.Read = shim_seek_read;
+  ms.s.Seek = shim_seek_seek;
+  ms.data = arc;
+  ms.size = size;
+  ms.pos = 0;
+  LookToRead_CreateVTable(&look, False);
+  look.realStream = &ms.s;
+  LookToRead_Init(&look);
+  saved = quiet_begin();
+  SzArEx_Init(&db);
+  res = SzArEx_Open(&db, &look.s, &g_shim_alloc, &g_shim_alloc);
+  *n_folders = 0;
+  *n_files = 0;
+  if (res == SZ_OK) {
+    *n_folders = db.db.NumFolders;
+    *n_files = db.db.NumFiles;
+    for (i = 0; i < db.db.NumFolders && i < folder_cap; i++) {
+      CSzFolder *f = db.db.Folders + i;
+      folders[5 * i] = f->NumCoders;
+      folders[5 * i + 1] = SzFolder_GetUnpackSize(f);
+      folders[5 * i + 2] = f->UnpackCRCDefined ? 1 : 0;
+      folders[5 * i + 3] = f->UnpackCRCDefined ? f->UnpackCRC : 0;
+      folders[5 * i + 4] = f->NumUnpackStreams;
+    }
+    for (i = 0; i < db.db.NumFiles && i < file_cap; i++) {
+      const CSzFileItem *f = db.db.Files + i;
+      files[5 * i] = f->HasStream ? 1 : 0;
+      files[5 * i + 1] = f->IsDir ? 1 : 0;
+      files[5 * i + 2] = f->CrcDefined ? 1 : 0;
+      files[5 * i + 3] = f->CrcDefined ? f->Crc : 0;
+      files[5 * i + 4] = db.FileIndexToFolderIndexMap ? db.FileIndexToFolderIndexMap[i] : 0xFFFFFFFF;
+    }
+  }
+  SzArEx_Free(&db, &g_shim_alloc);
+  quiet_end(saved);
   return res;
 }
 

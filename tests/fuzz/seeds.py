@@ -1,6 +1,6 @@
 """Seed corpora for the libFuzzer targets (TEST INFRASTRUCTURE): the committed
-golden fixtures and the hand-made xz files (tests/xz_handmade.py, generated),
-prefixed with the targets' selector bytes.
+golden fixtures and the hand-made xz files and 7z archives (tests/xz_handmade.py,
+tests/sz_handmade.py, generated), prefixed with the targets' selector bytes.
 
     python tests/fuzz/seeds.py OUTDIR   -> OUTDIR/containers/*, OUTDIR/lanes/*
 """
@@ -46,6 +46,9 @@ def write(out):
     import xz_handmade
     for c in xz_handmade.all_cases():
         put(con, b"\x01" + c["data"])
+    import sz_handmade
+    for c in sz_handmade.all_cases():
+        put(con, b"\x00" + c["data"])
     g = _load("cases.json", "blob.bin")
     for c in g["cases"][:300]:
         if c["kind"] not in ("lzma", "lzma2"):
